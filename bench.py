@@ -1,7 +1,13 @@
 """Benchmark: batched CarEnv.step throughput (car-steps/s = envs x cars x steps / s).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--cars C] [--track daytona] [--policy noisy]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, weak scaling)
+
+A plain run does only what the headline figure needs: set up and settle, warm up, time K steps, write the last
+step's outputs with --dump-outputs, print the result line.  --full adds everything else measured around it: the
+statistics and per-kernel passes (workload_stats, roofline), the per-step path, the drop-in API, the
+uniform-from-reset secondary and the CPU baseline.
 
 Headline workload (BASELINE.json metric "env-steps/sec (cars x envs), daytona 10-car"; SURVEY.md 8(d) action
 source (B)): E=8192 envs x C=10 cars on daytona.track per GPU, driven closed loop by the on-device noisy rule
@@ -10,11 +16,11 @@ replaced by a counter-hash uniform action), SB3-style auto-reset.  Before timing
 steady state: 10 800 steps (one 180 s episode) during which env e is reset at a staggered step, so that the
 env ages at the start of the timed window are spread uniformly over the episode -- cars are spread round the
 track, touch walls, complete laps, get disabled and auto-reset inside the timed window (the rates are reported
-in `workload_stats`).  A "step" = one env step over all E*C cars of a rank: model_logic_kernel (the noisy driver,
+in `workload_stats`, --full).  A "step" = one env step over all E*C cars of a rank: model_logic_kernel (the noisy driver,
 the vehicle + tyre model, the Box2D step and the env logic in one launch; nascar_set_fused_logic(h, 0) splits it
 into model_kernel + logic_kernel) then ray_sensor_kernel, issued on the sharded rollout schedule (4 env shards on 4
 streams, 50 steps per nascar_rollout call; bit-identical to one whole-batch launch per step).  The uniform-U[-1,1]^2-from-reset number of round 1 is kept
-only as the labelled secondary field `uniform_from_reset`.
+only as the labelled secondary field `uniform_from_reset` (--full).
 Prints ONE JSON line on rank 0 (schema: see DESIGN.md "Measurement").
 """
 import argparse
@@ -693,6 +699,29 @@ def drop_in_pass(E, C, track, rank, dev, steady, K=100, W=10, settle_steps=EPISO
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(env, directory):
+    """--dump-outputs: what the timed path's last step returned to its caller -- obs [E][C][38], reward [E][C],
+    car_flags [E][C] and env_flags [E] (the tuple of BatchedCarEnv.rollout / step) -- as DIR/<name>.npy in float32.
+    A batch over the size limit is cut to a fixed, seeded sample of its envs (the same rows of every array; their
+    indices in DIR/env_index.npy)."""
+    import numpy as np
+    arrays = {"obs": env.obs, "reward": env.reward, "car_flags": env.car_flags, "env_flags": env.env_flags}
+    per_env = 4 * sum(t.numel() // env.E for t in arrays.values()) + 8
+    keep = (DUMP_LIMIT_BYTES - 4096) // per_env            # (4096: the .npy headers)
+    idx = None
+    if keep < env.E:
+        idx = np.sort(np.random.default_rng(20261019).choice(env.E, keep, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float32)
+        np.save(os.path.join(directory, name + ".npy"), a if idx is None else a[idx])
+    if idx is not None:
+        np.save(os.path.join(directory, "env_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -733,6 +762,12 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=None)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything measured beside the headline: the statistics and per-kernel passes (workload_stats, "
+                         "roofline), the per-step path, the drop-in API, uniform-from-reset and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs (obs, reward, car_flags, env_flags "
+                         "of rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--plumbing", action="store_true", help="CPU tests: main() unchanged on a CPU stand-in engine "
                     "(PlumbingEngine: sleeps per step), gloo between the ranks; not a measurement")
     args = ap.parse_args()
@@ -814,9 +849,75 @@ def main():
     t_settle = time.perf_counter() - t_settle
     if args.save_state:
         torch.save({"state": env.get_state().cpu(), "obs": env.obs.cpu(), "step": base}, args.save_state)
+    fused = env.fused_logic
+    track_name = "mixed 8-track" if args.mixed else os.path.basename(tpath)[:-6]
+    settle_txt = (f", steady state after {S} settle steps" + (" (env ages staggered over the 180 s episode)"
+                  if closed and not args.no_stagger else "")) if S else (", from a saved steady state" if args.load_state
+                                                                        else ", from reset")
+    nshard = env.rollout_streams if step.R else 0
+    step_kernels = ("model_logic_kernel + ray_sensor_kernel" if fused
+                    else "model_kernel + logic_kernel + ray_sensor_kernel")
+    if not step.R:
+        launch_txt = "per-step kernels (nascar_step_driven)"
+        kernel_txt = f"{step_kernels} (one env step)"
+    elif nshard == 0:
+        launch_txt = f"fused rollout kernel, {step.R} steps per launch"
+        kernel_txt = f"rollout_kernel ({step.R} fused env steps per launch; per-step time)"
+    else:
+        launch_txt = (f"sharded rollout: {step.R} steps per nascar_rollout call, envs in {nshard} shards on {nshard} "
+                      f"streams (bit-identical to the per-step path)")
+        kernel_txt = (f"{step_kernels} over {nshard} env shards on {nshard} streams "
+                      f"(per-step time of a {step.R}-step rollout, HIP events on the caller's stream)")
+
+    def headline(elapsed, rank_elapsed):
+        """the result line of a plain run (elapsed: the MAX over the ranks' timed windows); --full adds to it"""
+        return {
+            "metric": "env-steps/sec (cars x envs), daytona 10-car",
+            "value": throughput(world, E, C, K, elapsed), "unit": "car-steps/s", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32+f64", "data": "synthetic",
+            "config": {"workload": f"{track_name} {C}-car: {E} envs x {C} cars per GPU, {POLICY_TEXT[args.policy]}"
+                                   f"{settle_txt}, auto-reset",
+                       "envs_per_gpu": E, "cars_per_env": C, "policy": args.policy,
+                       "launch": launch_txt,
+                       "car_contact": "on (build-only extension, no reference counterpart)" if args.car_contact else "off (reference)",
+                       "track": "mixed (env e: track e mod 8)" if args.mixed else os.path.basename(tpath),
+                       "parallelism": f"dp{world} (env shards" + ((", RCCL gather to rank 0 of every step's obs/reward/flags, one trajectory record per rollout call)" if step.R
+                                       else ", RCCL gather of obs/reward/flags to rank 0 per step)") if gather else ", no collective)")},
+            "ranks": {"world_size": dist.get_world_size() if world > 1 else 1,
+                      "backend": dist.get_backend() if world > 1 else None,
+                      "elapsed_s": rank_elapsed, "envs_per_block": env.envs_per_block,
+                      "note": "one process per GPU; each rank times its own K steps between barriers, value uses the MAX"},
+        }
+
+    def finish(out, env):
+        """the line's last entries, the same in a plain and a --full run, then print it (rank 0) and shut down"""
+        if tcache is not None:   # (after every timed window: the per-rank cache statistics of the engine starts)
+            out["track_cache"] = {"dir": tcache[0], "built": gather_all(tcache[1], dev), "loaded": gather_all(tcache[2], dev),
+                                  "prebuild_s": gather_all(tcache[3], dev),
+                                  "note": "per rank: tracks built into / loaded from the node's on-disk track cache before "
+                                          "the engine started (each track built once per node)"}
+        if args.plumbing:   # every rank must have issued the same collectives in the same order
+            seq = list(COLLECTIVES)
+            h = int(hashlib.sha256("|".join(seq).encode()).hexdigest()[:12], 16)
+            hs = gather_all(h, dev)
+            out["metric"] = "plumbing (no GPU, not a measurement)"
+            out["collectives"] = {"rank0": seq, "all_ranks_equal": len(set(hs)) == 1, "ranks": len(hs)}
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        env.close()
+        if world > 1:
+            dist.destroy_process_group()
+
     step.gather = gather
     step.run(base, W)
     elapsed = timed(step, base + W, K, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs)
+    if not args.full:   # the plain run: the headline alone
+        rank_elapsed = gather_all(elapsed, dev)
+        finish(headline(reduce_max([elapsed], dev)[0], rank_elapsed), env)
+        return
     KR = min(K, 50)
     kern_ms, tally, KT = stats_pass(env, step, base + W + K, KR)   # KT: the steps the tallies cover
     ktimes = kernel_pass(env, Stepper(env, args.policy, rank, acts, None, 0), base + W + K + 2 * KR, KR)
@@ -830,7 +931,6 @@ def main():
         next_step = first + W + K
     rank_elapsed = gather_all(elapsed, dev)
     elapsed, kern_ms = reduce_max([elapsed, kern_ms], dev)
-    fused = env.fused_logic
     if fused:   # model_logic_kernel between events 0 and 1 (events 1 and 2 are recorded back to back)
         ktimes = {"model_logic_kernel": ktimes["model_kernel"], "ray_sensor_kernel": ktimes["ray_sensor_kernel"]}
     kt_names = tuple(ktimes)
@@ -840,7 +940,6 @@ def main():
     if per_step is not None:
         per_step = reduce_max([per_step], dev)[0]
     tally = reduce_sum(tally, dev)
-    value = throughput(world, E, C, K, elapsed)
     # dominant kernel (model_kernel, whole grid): ITS algorithmic bytes per car (the state it reads and writes + the
     # action) x the cars one launch processes, over its mean launch duration (HIP events around it on its stream,
     # per-step path).  The whole step's bytes over the timed window's step time are `roofline.step`.
@@ -869,37 +968,8 @@ def main():
               "contact_frac": tally[0] / ncs, "lap_completed_frac": tally[1] / ncs, "disabled_frac": tally[2] / ncs,
               "just_disabled_frac": tally[3] / ncs, "env_reset_frac": tally[4] / (world * E * KT),
               "mean_speed_ms": tally[6] / ncs * 111.1, "settle_s": t_settle}
-    track_name = "mixed 8-track" if args.mixed else os.path.basename(tpath)[:-6]
-    settle_txt = (f", steady state after {S} settle steps" + (" (env ages staggered over the 180 s episode)"
-                  if closed and not args.no_stagger else "")) if S else (", from a saved steady state" if args.load_state
-                                                                        else ", from reset")
-    nshard = env.rollout_streams if step.R else 0
-    step_kernels = ("model_logic_kernel + ray_sensor_kernel" if fused
-                    else "model_kernel + logic_kernel + ray_sensor_kernel")
-    if not step.R:
-        launch_txt = "per-step kernels (nascar_step_driven)"
-        kernel_txt = f"{step_kernels} (one env step)"
-    elif nshard == 0:
-        launch_txt = f"fused rollout kernel, {step.R} steps per launch"
-        kernel_txt = f"rollout_kernel ({step.R} fused env steps per launch; per-step time)"
-    else:
-        launch_txt = (f"sharded rollout: {step.R} steps per nascar_rollout call, envs in {nshard} shards on {nshard} "
-                      f"streams (bit-identical to the per-step path)")
-        kernel_txt = (f"{step_kernels} over {nshard} env shards on {nshard} streams "
-                      f"(per-step time of a {step.R}-step rollout, HIP events on the caller's stream)")
-    out = {
-        "metric": "env-steps/sec (cars x envs), daytona 10-car",
-        "value": value, "unit": "car-steps/s", "n_gpus": world, "steps": K, "warmup": W,
-        "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32+f64", "data": "synthetic",
-        "config": {"workload": f"{track_name} {C}-car: {E} envs x {C} cars per GPU, {POLICY_TEXT[args.policy]}"
-                               f"{settle_txt}, auto-reset",
-                   "envs_per_gpu": E, "cars_per_env": C, "policy": args.policy,
-                   "launch": launch_txt,
-                   "car_contact": "on (build-only extension, no reference counterpart)" if args.car_contact else "off (reference)",
-                   "track": "mixed (env e: track e mod 8)" if args.mixed else os.path.basename(tpath),
-                   "parallelism": f"dp{world} (env shards" + ((", RCCL gather to rank 0 of every step's obs/reward/flags, one trajectory record per rollout call)" if step.R
-                                   else ", RCCL gather of obs/reward/flags to rank 0 per step)") if gather else ", no collective)")},
+    out = headline(elapsed, rank_elapsed)
+    out.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tnote,
                      "kernel": f"{dom} (dominant kernel; whole-grid launch on the per-step path, HIP events around "
@@ -921,11 +991,7 @@ def main():
                      "timed_path_event_note": kernel_txt},
         "workload_stats": wstats,
         "engine_errors": int(tally[5]),
-        "ranks": {"world_size": dist.get_world_size() if world > 1 else 1,
-                  "backend": dist.get_backend() if world > 1 else None,
-                  "elapsed_s": rank_elapsed, "envs_per_block": env.envs_per_block,
-                  "note": "one process per GPU; each rank times its own K steps between barriers, value uses the MAX"},
-    }
+    })
     if per_step is not None:
         out["per_step"] = {"value": throughput(world, E, C, K, per_step), "ms_per_step": per_step / K * 1e3,
                            "note": "secondary: the same envs and driver stepped by one whole-batch launch per step "
@@ -955,25 +1021,10 @@ def main():
                                      "note": "secondary: uniform actions from reset (cars stay on the start "
                                              "straight; no contacts, laps or resets) -- an upper bound, not the headline"}
         env = env2
-    if tcache is not None:   # (after every timed window: the per-rank cache statistics of the engine starts)
-        out["track_cache"] = {"dir": tcache[0], "built": gather_all(tcache[1], dev), "loaded": gather_all(tcache[2], dev),
-                              "prebuild_s": gather_all(tcache[3], dev),
-                              "note": "per rank: tracks built into / loaded from the node's on-disk track cache before "
-                                      "the engine started (each track built once per node)"}
-    if args.plumbing:   # every rank must have issued the same collectives in the same order
-        seq = list(COLLECTIVES)
-        h = int(hashlib.sha256("|".join(seq).encode()).hexdigest()[:12], 16)
-        hs = gather_all(h, dev)
-        out["metric"] = "plumbing (no GPU, not a measurement)"
-        out["collectives"] = {"rank0": seq, "all_ranks_equal": len(set(hs)) == 1, "ranks": len(hs)}
     if cpu_leg:
         out["cpu_baseline"] = cpu_baseline(tpath, C, args.cpu_budget, args.cpu_threads,
                                            steady if args.policy == "noisy" and not args.mixed else None)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    env.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish(out, env)
 
 
 if __name__ == "__main__":

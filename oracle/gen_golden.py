@@ -19,9 +19,11 @@ Usage:  python oracle/gen_golden.py [--ref /root/reference] [--out tests/golden]
 """
 import argparse
 import ctypes
+import io
 import os
 import sys
 import types
+import zipfile
 
 import numpy as np
 
@@ -629,10 +631,26 @@ def main():
         if args.only not in (None, name) and not (args.only == "new" and extra is not None and name in NEW):
             continue
         d = run_scenario(args.ref, name, track, C, steps, pol, rol, rat, **(extra[0] if extra else {}))
-        np.savez_compressed(os.path.join(args.out, f"env_{name}.npz"), **d)
+        path = os.path.join(args.out, f"env_{name}.npz")
+        np.savez_compressed(path, **d)
+        if os.path.getsize(path) > MAX_FIXTURE_BYTES:     # the long traces: LZMA members pack a third smaller
+            savez_lzma(path, **d)
         term = d["terminated"].nonzero()[0]
         print(name, "steps", len(d["obs"]), "laps", np.nanmax(d["info"][..., 0]), "disabled", d["info"][-1, :, 8],
               "first-term", term[:1], "reasons", np.unique(d["reason"]))
+
+
+MAX_FIXTURE_BYTES = 1 << 20       # no committed file may be larger
+
+
+def savez_lzma(path, **arrays):
+    """np.savez_compressed with LZMA members (np.load reads them as any .npz; needs Python's lzma module): for the
+    traces that deflate leaves over MAX_FIXTURE_BYTES (env_martinsville_lap, env_talladega_10car)"""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_LZMA) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.save(buf, np.asanyarray(v))
+            z.writestr(k + ".npy", buf.getvalue())
 
 
 if __name__ == "__main__":

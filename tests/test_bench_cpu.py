@@ -69,7 +69,7 @@ def _bench(args, env=None, timeout=240):
 
 @pytest.mark.parametrize("gather", [False, True])
 def test_gpus_n_runs_main_on_n_ranks(gather):
-    """`bench.py --gpus 2 --plumbing` outside torchrun starts 2 ranks itself (torch.distributed.run child) and runs
+    """`bench.py --gpus 2 --plumbing --full` outside torchrun starts 2 ranks itself (torch.distributed.run child) and runs
     bench.main() unchanged on the CPU stand-in engine (PlumbingEngine) over gloo: the settle, the warm-up, the
     barrier-bracketed timed window, the statistics and kernel passes, the per-step pass, the secondary pass and every
     collective main() issues (gather_all, the reduce_max / reduce_sum calls, the barriers), with and without the
@@ -78,7 +78,7 @@ def test_gpus_n_runs_main_on_n_ranks(gather):
     same order."""
     import json
     K, E, C = 6, 16, 10
-    args = ["--gpus", "2", "--plumbing", "--steps", str(K), "--warmup", "2", "--envs", str(E), "--cars", str(C),
+    args = ["--gpus", "2", "--plumbing", "--full", "--steps", str(K), "--warmup", "2", "--envs", str(E), "--cars", str(C),
             "--settle", "12"] + (["--gather"] if gather else [])
     r = _bench(args)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -109,6 +109,61 @@ def test_gpus_n_runs_main_on_n_ranks(gather):
     assert d["per_step"]["ms_per_step"] >= 2.0
     ws = d["workload_stats"]
     assert ws["window_car_steps"] > 0 and 0 < ws["contact_frac"] < 1
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the timed window and nothing beside it (no statistics,
+    kernel, per-step, secondary or CPU-baseline pass: none of their fields, and the engine has stepped settle + W + K
+    times), ms_per_step the window's time over K.  --dump-outputs DIR writes the last timed step's outputs as float32
+    .npy files, the same from run to run."""
+    import json
+    K, W, S, E, C = 5, 2, 3, 16, 10
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = _bench(["--gpus", "1", "--plumbing", "--steps", str(K), "--warmup", str(W), "--envs", str(E), "--cars", str(C),
+                    "--settle", str(S), "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        line = json.loads(lines[0])
+        assert set(line) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                             "scaling", "vs_baseline", "dtype", "data", "config", "ranks", "collectives"}
+        assert line["steps"] == K and line["warmup"] == W and line["unit"] == "car-steps/s" and line["higher_is_better"]
+        assert line["ms_per_step"] >= 1.0          # rank 0 sleeps 1 ms per step
+        assert np.isclose(line["value"], E * C / (line["ms_per_step"] * 1e-3))
+        assert line["collectives"]["rank0"] == []
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["car_flags.npy", "env_flags.npy", "obs.npy", "reward.npy"]
+    assert a["obs.npy"].shape == (E, C, 38) and a["reward.npy"].shape == (E, C) and a["env_flags.npy"].shape == (E,)
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    # the stand-in engine writes the step index into obs: the last timed step is step S + W + K - 1, and nothing ran after
+    assert a["obs.npy"][0, 0, 0] == S + W + K - 1
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_dump_outputs_samples_a_large_batch(tmp_path):
+    """a batch over the size limit is cut to the same seeded sample of envs in every array, within the limit"""
+    import torch
+    eng = bench.PlumbingEngine(4096, 2, 0, "cpu")
+    eng.obs.copy_(torch.arange(4096.0).view(-1, 1, 1).expand(4096, 2, 38))
+    eng.env_flags.copy_(torch.arange(4096) % 251)
+    lim = bench.DUMP_LIMIT_BYTES
+    try:
+        bench.DUMP_LIMIT_BYTES = 64 << 10
+        bench.dump_outputs(eng, str(tmp_path / "a"))
+        bench.dump_outputs(eng, str(tmp_path / "b"))
+    finally:
+        bench.DUMP_LIMIT_BYTES = lim
+    a = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in a) <= 64 << 10
+    idx = a["env_index.npy"].astype(np.int64)
+    assert 100 < idx.size < 4096 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a["obs.npy"][:, 0, 0], idx) and np.array_equal(a["env_flags.npy"], idx % 251)
+    assert a["reward.npy"].shape == (idx.size, 2)
+    assert all(np.array_equal(a[f], np.load(tmp_path / "b" / f)) for f in a)
 
 
 def test_world_size_mismatch_is_an_error():

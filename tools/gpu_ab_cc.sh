@@ -15,6 +15,6 @@ for rep in 1 2 3; do
 done
 for v in fused split; do
   if [ $v = split ]; then L=tools/build/libnascar_ccsplit.so; else L=nascargymnasium_amd/libnascar.so; fi
-  NASCAR_LIB=$L timeout -k 10 300 python bench.py $B --track talladega --car-contact --steps 200 --warmup 20 > "$OUT/cc_$v.log" 2>&1; stop $? "cc $v"
+  NASCAR_LIB=$L timeout -k 10 300 python bench.py --full $B --track talladega --car-contact --steps 200 --warmup 20 > "$OUT/cc_$v.log" 2>&1; stop $? "cc $v"
   echo "cc $v $(grep -o '"ms_per_step": [0-9.]*' "$OUT/cc_$v.log" | head -2 | tr '\n' ' ')"
 done
