@@ -121,7 +121,8 @@ int nascar_step(NascarHandle* h, const void* actions, int32_t discrete, float* o
 
 /* nascar_step with the actions of device action source `policy` (0, 1, 3: see nascar_policy_actions) computed on
  * the current obs inside the step launch -- one closed-loop driver step (game/control drivers' loop) without a
- * separate action launch; identical results to nascar_policy_actions(policy, seed, step) + nascar_step. */
+ * separate action launch; identical results to nascar_policy_actions(policy, seed, step) + nascar_step.  Policies 2
+ * and 4 (the MLP controllers) are not available here: use nascar_policy_actions + nascar_step, or nascar_rollout. */
 int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, float* obs, float* reward,
                        uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs, void* stream);
 
@@ -134,7 +135,10 @@ int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed, int64_t s
  *   policy:  0 uniform, 1 BaseController._fallback_control, 3 noisy rule driver (policy 1 with 15 % of the
  *            car-steps uniform) -- see nascar_policy_actions; 2 the SAC actor (nascar_set_actor; sharded
  *            rollout only: each shard runs the actor on its own cars, one shard unless the envs sit in one
- *            track's workgroups in order)
+ *            track's workgroups in order); 4 the field of nascar_set_car_controllers (sharded rollout only, as
+ *            policy 2: each shard runs the field on its own envs, one shard when the envs do not sit in one track's
+ *            workgroups in order or random tracks are on; streams = 0 fails, and under nascar_set_rollout_pipe the
+ *            streams setting applies)
  *   obs:     [E*C*38] float32, in: the current observation, out: the last step's
  *   traj & NASCAR_TRAJ_RECORDS: reward [steps][E*C], car_flags [steps][E*C], env_flags [steps][E] (per-step records);
  *   traj == 0: reward [E*C], car_flags [E*C], env_flags [E] hold the last step's values.
@@ -161,7 +165,7 @@ int nascar_get_rollout_streams(NascarHandle* h);
  * Box2D step and the env logic K times, and `sensor_workgroups` sensor workgroups taking each group's sensor work from
  * a device queue as the group publishes it -- so every group goes on to its next step as soon as its own sensors are
  * done instead of waiting for the batch's slowest car.  Applies to policies 0, 1, 3 without random tracks, car
- * contact or obs trajectories (the streams setting applies otherwise); 0 turns it off (default).  Every device wait
+ * contact or obs trajectories (the streams setting applies otherwise, so to policies 2 and 4); 0 turns it off (default).  Every device wait
  * is clock-bounded: nascar_rollout_pipe_status waits for `stream` and returns 1 if a pipelined rollout since the
  * last status call gave up (its results are not valid), 0 if not, -1 on error. */
 int nascar_set_rollout_pipe(NascarHandle* h, int32_t sensor_workgroups);
@@ -213,9 +217,12 @@ int nascar_get_info(NascarHandle* h, double* info, void* stream);
 
 /* BUILD-ONLY EXTENSION, no reference counterpart (each reference car has its own b2World, so cars never touch):
  * enable != 0 makes the cars of an env collide -- staggered start grid (rows of 2, 8 m apart), and after each
- * Box2D step a frictionless central impulse (restitution 0.25) between overlapping, closing car boxes, counted in
- * the cars' collision impulse (damage / impact disables).  Default 0 (reference behaviour); parity runs with 0.
- * Takes effect from the next reset (start grid) and step. */
+ * Box2D step the env's touching car pairs (b2CollidePolygons manifolds of the car boxes, 1-2 points each) are solved
+ * with b2ContactSolver's sequential impulses for two dynamic bodies: 6 velocity iterations of friction (mixed
+ * coefficient 0.7) then normal impulses, restitution 0.1 above Box2D's 1 m/s velocity threshold, applied to both cars'
+ * linear and angular velocity, after (not interleaved with) each car's wall island, without warm start or position
+ * correction.  The normal impulses count in the cars' collision impulse (damage / impact disables).  Default 0
+ * (reference behaviour); parity runs with 0.  Takes effect from the next reset (start grid) and step. */
 int nascar_set_car_contact(NascarHandle* h, int32_t enable);
 
 /* Car.velocity_history for Car.validate_performance (src/car.py:173, 384-386, 1060-1098): enable != 0 keeps
@@ -234,7 +241,13 @@ int nascar_set_state(NascarHandle* h, const void* src_device, void* stream);
  *   policy 1: BaseController._fallback_control (game/control/base_controller.py:39-103) from obs
  *   policy 2: the SAC actor loaded with nascar_set_actor, deterministic (SACController.control,
  *             game/control/sac_control_class.py:80-115) from obs
- *   policy 3: policy 1 with its action replaced by policy 0's draw on 15 % of the car-steps (counter hash) */
+ *   policy 3: policy 1 with its action replaced by policy 0's draw on 15 % of the car-steps (counter hash)
+ *   policy 4: "the field" -- the car in slot c of every env takes its action from ctrl[c] of
+ *             nascar_set_car_controllers: a controller (nascar_add_controller) on that car's obs, or a built-in source,
+ *             which produces exactly what policy 0, 1 or 3 produces for that car at the same (seed, step), the rule
+ *             driver's per-car control state included; slots driven by a controller leave that state untouched.  One
+ *             launch per distinct (h1, h2, activation) among the field's controllers plus one for the built-in slots,
+ *             however many controllers are loaded.  Fails without a table.  actions 8-byte aligned. */
 int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, const float* obs,
                           float* actions, void* stream);
 
@@ -252,6 +265,48 @@ int nascar_set_actor(NascarHandle* h, const float* w1, const float* b1, const fl
 int nascar_set_actor_precision(NascarHandle* h, int32_t fp32);
 /* The loaded actor on any device batch: obs [n][38] float32 -> actions [n][2] float32 (both 8-byte aligned). */
 int nascar_actor_forward(NascarHandle* h, const float* obs, int32_t n, float* actions, void* stream);
+
+/* Per-car controllers: the reference's race modes put a different controller in every car of an env
+ * (game/competition.py:150-212, 285-307; game/championship.py and game/time_trial.py likewise: one controller per car,
+ * controller.control(obs[car_idx]) for each car before every env.step).  A controller here is a float32 MLP
+ * obs[38] -> h1 -> h2 -> 2 actions run on the f32 MFMA (mlp_field_kernel, csrc/nascar_actor.h), covering every SB3
+ * checkpoint kind the reference ships (game/control/models/):
+ *   sac_*.zip             256-256, ReLU, output 2 (tanh-squashed, then unscale_action)   SACController.control
+ *   ppo_789 / ppo_849     64-64, Tanh, output 1 (the mean clipped to the Box)            PPOController.control
+ *   a2c_best_model3.zip   256-128, ReLU, output 1                                        A2CController.control
+ * (A2CController predicts on the raw observation although the checkpoint was trained under VecNormalize,
+ * game/control/a2c_control_class.py:104-111; this library does what the controller does.)
+ * NascarMlp: host float32 arrays in PyTorch layouts, w1 [h1][38], b1 [h1], w2 [h2][h1], b2 [h2], w3 [2][h2], b3 [2];
+ *   activation 0 ReLU, 1 Tanh (tanhf in float32), on both hidden layers;
+ *   output 0 raw: mu = W3 h + b3;  1 clip: min(max(mu, -1), 1), SB3 predict for an unsquashed Box policy;
+ *          2 squash: tanh(mu) followed by BasePolicy.unscale_action for the Box(-1, 1), as policy 2.
+ * Shapes: obs_dim 38, act_dim 2 and (h1, h2) one of 256-256, 256-128, 256-32, 128-128, 64-64, 32-256; every other
+ * shape is rejected with a message naming it -- TD3's SB3 default [400, 300] included (the reference ships no TD3
+ * checkpoint; nor is the genetic controller covered: GeneticController.control raises).
+ * nascar_check_controller (host only, no device, h not needed): 0 if nascar_add_controller would accept the shape,
+ *   activation and output, < 0 with the message otherwise.
+ * nascar_add_controller: copies the weights to the device; returns the controller's id >= 0 (at most 16 per handle;
+ *   ids stay valid for the handle's life).
+ * nascar_controller_forward: controller `id` on any device batch, obs [n][38] -> actions [n][2] float32 (actions
+ *   8-byte aligned).  256-256 ReLU with output 2 performs the float32 policy-2 kernel's operations in its order: the
+ *   results are equal bit for bit.
+ * nascar_set_car_controllers: ctrl is a host array [C]: the car in slot c of every env is driven by ctrl[c], a
+ *   controller id or one of the built-in sources below; NULL clears the table.  The table is what policy 4 ("the
+ *   field") of nascar_policy_actions and nascar_rollout runs; an id that was never returned by nascar_add_controller,
+ *   or a negative value other than the three below, is an error. */
+typedef struct NascarMlp {
+    int32_t obs_dim, h1, h2, act_dim;
+    int32_t activation;      /* 0 ReLU, 1 Tanh */
+    int32_t output;          /* 0 raw, 1 clip, 2 squash */
+    const float *w1, *b1, *w2, *b2, *w3, *b3;   /* PyTorch layouts, host */
+} NascarMlp;
+#define NASCAR_CTRL_RULE (-1)      /* policy 1 */
+#define NASCAR_CTRL_UNIFORM (-2)   /* policy 0 */
+#define NASCAR_CTRL_NOISY (-3)     /* policy 3 */
+int nascar_check_controller(const NascarMlp* mlp);
+int nascar_add_controller(NascarHandle* h, const NascarMlp* mlp);
+int nascar_controller_forward(NascarHandle* h, int32_t id, const float* obs, int32_t n, float* actions, void* stream);
+int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl);
 
 /* Test hook: the device re-implementation of glibc sinf/cosf used for b2Rot::Set
  * (device pointers, n floats).  Parity tests compare it with the host libm. */

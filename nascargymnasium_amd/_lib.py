@@ -34,6 +34,15 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-m
                "-shared", "-std=c++17", "-Wno-unused-value", "-Wno-unused-result"]
 
 
+class NascarMlp(ctypes.Structure):
+    """include/nascar.h NascarMlp: one MLP controller, host float32 arrays in PyTorch layouts."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("obs_dim", "h1", "h2", "act_dim", "activation", "output")] + \
+               [(n, ctypes.POINTER(ctypes.c_float)) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
+
+
+CTRL_BUILTIN = {"rule": -1, "uniform": -2, "noisy": -3}   # NASCAR_CTRL_RULE / _UNIFORM / _NOISY
+
+
 class NascarConfig(ctypes.Structure):
     _fields_ = [("num_envs", ctypes.c_int32), ("num_cars", ctypes.c_int32), ("reset_on_lap", ctypes.c_int32),
                 ("device", ctypes.c_int32), ("start_x", ctypes.c_double), ("start_y", ctypes.c_double),
@@ -125,6 +134,14 @@ def lib():
     L.nascar_set_actor_precision.restype = ctypes.c_int
     L.nascar_actor_forward.argtypes = [vp, vp, i32, vp, vp]
     L.nascar_actor_forward.restype = ctypes.c_int
+    L.nascar_check_controller.argtypes = [ctypes.POINTER(NascarMlp)]
+    L.nascar_check_controller.restype = ctypes.c_int
+    L.nascar_add_controller.argtypes = [vp, ctypes.POINTER(NascarMlp)]
+    L.nascar_add_controller.restype = ctypes.c_int
+    L.nascar_controller_forward.argtypes = [vp, i32, vp, i32, vp, vp]
+    L.nascar_controller_forward.restype = ctypes.c_int
+    L.nascar_set_car_controllers.argtypes = [vp, ctypes.POINTER(i32)]
+    L.nascar_set_car_controllers.restype = ctypes.c_int
     L.nascar_set_step_events.argtypes = [vp, ctypes.POINTER(vp), i32]
     L.nascar_set_step_events.restype = ctypes.c_int
     L.nascar_debug_sincosf.argtypes = [vp, vp, vp, i32, vp]
@@ -158,6 +175,7 @@ def lib():
 EXPORTED = ["nascar_create", "nascar_destroy", "nascar_last_error", "nascar_add_track", "nascar_set_env_tracks",
             "nascar_reset", "nascar_step", "nascar_step_driven", "nascar_rollout", "nascar_get_info", "nascar_set_perf_history", "nascar_set_car_contact", "nascar_set_rollout_streams", "nascar_get_rollout_streams", "nascar_set_rollout_pipe", "nascar_rollout_pipe_status", "nascar_set_envs_per_block", "nascar_get_envs_per_block", "nascar_set_sensor_lanes", "nascar_set_sensor_block", "nascar_set_beam_cell", "nascar_set_fused_logic", "nascar_get_fused_logic", "nascar_state_bytes", "nascar_get_state",
             "nascar_set_state", "nascar_policy_actions", "nascar_set_step_events", "nascar_set_actor", "nascar_set_actor_precision", "nascar_actor_forward",
+            "nascar_check_controller", "nascar_add_controller", "nascar_controller_forward", "nascar_set_car_controllers",
             "nascar_debug_sincosf", "nascar_debug_sensors", "nascar_track_draw", "nascar_set_random_tracks",
             "nascar_get_env_tracks", "nascar_vec_post", "nascar_check_actions", "nascar_set_track_cache",
             "nascar_prebuild_track", "nascar_debug_block_map"]
@@ -167,6 +185,24 @@ def check(rc):
     if rc < 0:
         raise RuntimeError("libnascar: " + lib().nascar_last_error().decode())
     return rc
+
+
+def mlp_struct(ctrl):
+    """(NascarMlp, the arrays it points to) for a nascargymnasium_amd.policy.Controller; keep the arrays alive while
+    the struct is in use."""
+    import numpy as np
+    arrs = [np.ascontiguousarray(a, np.float32) for a in ctrl.arrays]
+    fp = ctypes.POINTER(ctypes.c_float)
+    m = NascarMlp(38, int(ctrl.h1), int(ctrl.h2), 2, int(ctrl.activation), int(ctrl.output),
+                  *[a.ctypes.data_as(fp) for a in arrs])
+    return m, arrs
+
+
+def check_controller(ctrl):
+    """nascar_check_controller (host only, no GPU): raises RuntimeError naming the shape unless add_controller would
+    accept this controller's shape, activation and output."""
+    m, _keep = mlp_struct(ctrl)
+    check(lib().nascar_check_controller(ctypes.byref(m)))
 
 
 def track_draw(seeds, k, current, tracks):

@@ -99,7 +99,7 @@ class BatchedCarEnv:
         """Pipelined `rollout` (identical results): each workgroup of envs goes on to its next step as soon as its own
         sensors are done, with the sensors in a second persistent kernel of `sensor_workgroups` workgroups fed from a
         device queue, so a slow car delays only its own envs (not the batch's step).  0 turns it off.  Used by
-        `rollout` for policies 0 / 1 / 3 without random tracks, car contact or obs trajectories (else the setting of
+        `rollout` for policies 0 / 1 / 3 (not 2 or 4) without random tracks, car contact or obs trajectories (else the setting of
         set_rollout_streams applies)."""
         _lib.check(self.L.nascar_set_rollout_pipe(self.h, int(sensor_workgroups)))
         self.rollout_pipe = int(sensor_workgroups)
@@ -270,7 +270,7 @@ class BatchedCarEnv:
     def step_driven(self, policy: int, seed: int = 0, step: int = 0, auto_reset: bool = True, terminal_obs: bool = False):
         """One env step whose actions come from device action source `policy` (0 uniform, 1 rule driver, 3 noisy rule
         driver) on the current obs, computed inside the step launch; equals policy_actions(policy, seed, step) +
-        step(...)."""
+        step(...).  Policies 2 and 4 (MLP controllers) raise: use policy_actions + step, or rollout."""
         with torch.cuda.device(self.device):
             _lib.check(self.L.nascar_step_driven(self.h, int(policy), int(seed), int(step), _ptr(self.obs), _ptr(self.reward),
                                                  _ptr(self.car_flags), _ptr(self.env_flags), int(auto_reset),
@@ -281,7 +281,7 @@ class BatchedCarEnv:
                 trajectory: bool = False, out=None, obs_trajectory: bool = False):
         """`steps` env steps in one call (sharded over streams, or one fused launch: set_rollout_streams), actions
         from device action source `policy` (0 uniform, 1 rule driver, 2 the SAC actor -- sharded only, 3 noisy rule
-        driver) on the previous observation; equals `steps` x (policy_actions(policy, seed, step0 + k) +
+        driver, 4 the field of per-car controllers, set_car_controllers -- sharded only) on the previous observation; equals `steps` x (policy_actions(policy, seed, step0 + k) +
         step(..., auto_reset)).  Returns (obs, reward, car_flags, env_flags): the last step's, or with
         trajectory=True the per-step records [steps, E, C] / [steps, E] (obs the last step's).  obs_trajectory=True
         (with trajectory=True, sharded rollout only) also records every step's observation: obs [steps + 1, E, C, 38],
@@ -394,8 +394,47 @@ class BatchedCarEnv:
             _lib.check(self.L.nascar_actor_forward(self.h, _ptr(o), n, _ptr(out), _stream()))
         return out
 
+    # ------------------------------------------------------------------ per-car controllers (policy 4, "the field")
+    def add_controller(self, ctrl) -> int:
+        """Load one MLP controller (nascargymnasium_amd.policy.Controller: load_sb3_policy for the reference's SAC /
+        PPO / A2C checkpoints, random_mlp) onto the device; returns its id for set_car_controllers /
+        controller_forward.  At most 16 per env; shapes the kernels do not hold (_lib.check_controller) raise."""
+        m, _keep = _lib.mlp_struct(ctrl)
+        with torch.cuda.device(self.device):
+            return _lib.check(self.L.nascar_add_controller(self.h, ctypes.byref(m)))
+
+    def controller_forward(self, cid: int, obs: torch.Tensor) -> torch.Tensor:
+        """Controller `cid` on a device batch of observations [..., 38] -> actions [..., 2] (float32 MFMA kernel)."""
+        o = obs.to(self.device, torch.float32).contiguous()
+        n = o.numel() // 38
+        out = torch.empty(o.shape[:-1] + (2,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.nascar_controller_forward(self.h, int(cid), _ptr(o), n, _ptr(out), _stream()))
+        return out
+
+    def set_car_controllers(self, ctrl=None):
+        """The field: the car in slot c of every env is driven by ctrl[c] -- a controller id from add_controller, or
+        "rule" (policy 1), "uniform" (policy 0), "noisy" (policy 3) -- as the reference's race modes build one controller
+        per car (game/competition.py:150-212).  policy_actions(4) and rollout(4, ...) then run it.  None clears it."""
+        if ctrl is None:
+            _lib.check(self.L.nascar_set_car_controllers(self.h, None))
+            return
+        ctrl = list(ctrl)
+        if len(ctrl) != self.C:
+            raise ValueError(f"need one controller per car slot ({self.C}), got {len(ctrl)}")
+        codes = []
+        for c in ctrl:
+            if isinstance(c, str):
+                if c not in _lib.CTRL_BUILTIN:
+                    raise ValueError(f"unknown built-in controller {c!r} (one of {sorted(_lib.CTRL_BUILTIN)})")
+                c = _lib.CTRL_BUILTIN[c]
+            codes.append(int(c))
+        arr = (ctypes.c_int32 * self.C)(*codes)
+        _lib.check(self.L.nascar_set_car_controllers(self.h, arr))
+
     def policy_actions(self, policy: int, seed: int = 0, step: int = 0, obs: Optional[torch.Tensor] = None):
-        """device-generated actions: 0 uniform U[-1,1]^2, 1 BaseController fallback driver, 2 the SAC actor."""
+        """device-generated actions: 0 uniform U[-1,1]^2, 1 BaseController fallback driver, 2 the SAC actor, 3 the noisy
+        rule driver, 4 the field of per-car controllers (set_car_controllers)."""
         o = self.obs if obs is None else obs
         with torch.cuda.device(self.device):
             _lib.check(self.L.nascar_policy_actions(self.h, int(policy), int(seed), int(step), _ptr(o),

@@ -315,6 +315,141 @@ actor_mfma32_kernel(int N, const float* __restrict__ obs, float* __restrict__ ac
   }
 }
 
+// ------------------------------------------------------------------ per-car controllers (policy 4): the general f32 MLP
+// The reference's race modes put a different controller in every car of an env (game/competition.py:150-212, 285-307:
+// one controller per car, controller.control(obs[car_idx]) before every env.step): SB3 SAC, PPO and A2C checkpoints
+// beside the rule driver.  mlp_field_kernel is actor_mfma32_kernel generalised to every model the reference ships
+// (game/control/models/): a float32 MLP  obs[38] -> h1 -> h2 -> 2  on v_mfma_f32_32x32x2_f32, templated on the hidden
+// tile counts T1 = h1 / 32 and T2 = h2 / 32 and on the activation; the output transform is a template of the epilogue
+// (mlp_out<OUT>), chosen per controller by a wave-uniform switch, so that controllers that differ only in it share a
+// launch.
+//   activation  MLP_RELU, or MLP_TANH with tanhf in f32 (SB3's ActorCriticPolicy default, the PPO checkpoints)
+//   output      MLP_OUT_RAW    mu = W3 h + b3
+//               MLP_OUT_CLIP   min(max(mu, -1), 1): SB3 predict for an unsquashed Box policy (PPO, A2C)
+//               MLP_OUT_SQUASH tanh(mu), then unscale_action for the Box(-1, 1) (SAC; actor_mfma32_kernel's expression)
+// Shapes: obs_dim 38 and act_dim 2; (h1, h2) one of MLP_SHAPES below -- 256-256 (the SAC checkpoints), 64-64 (ppo_789,
+// ppo_849), 256-128 (a2c_best_model3), and 128-128, 256-32, 32-256 for other nets; every other shape is rejected when the
+// controller is loaded (mlp_shape_ok), with a message naming it.  That includes TD3's SB3 default [400, 300]: no multiple
+// of 32, and the reference ships no TD3 checkpoint.
+// Addressing: one wave = one tile = 32 consecutive envs at ONE car slot c, so the controller is wave-uniform: row i of
+// the tile is car (env0 + i) * C + c, its observation C * 38 floats after row i - 1's, its action at [car][2].  The
+// kernel covers the env range [env0, env0 + nenv) (a rollout shard runs it on its own envs); the last tile of the range
+// may be ragged: its extra lanes load the range's last row and store nothing.  blockIdx.y picks the (slot, controller)
+// pair of the launch; the weights come from the device table of controllers (scalar loads: the index is uniform).
+// With C = 1 and c = 0 the rows are a flat batch: nascar_controller_forward.
+// Launches: one per distinct (T1, T2, activation) among a field's controllers (at most the instantiations below,
+// however many controllers are loaded) -- not one kernel with a switch over the instantiations, which would run the
+// 64-64 nets at the 256-256 net's one wave per SIMD.
+// <8, 8, MLP_RELU> with MLP_OUT_SQUASH performs actor_mfma32_kernel's operations in its order (k order of all three
+// layers, bias after the accumulation, the lane-half add, tanhf, unscale_action): an all-SAC field equals policy 2 in
+// fp32 bit for bit (tests/test_gpu_field.py).  Register budget: 16 (T1 + T2) accumulator / operand VGPRs.
+#define MLP_MAX_CTRL 16    // controllers per handle
+#define MLP_MAX_CARS 64    // car slots per env (nascar_create's limit)
+enum { MLP_RELU = 0, MLP_TANH = 1 };
+enum { MLP_OUT_RAW = 0, MLP_OUT_CLIP = 1, MLP_OUT_SQUASH = 2 };
+#define MLP_SHAPES(X) X(8, 8) X(8, 4) X(8, 1) X(4, 4) X(2, 2) X(1, 8)
+struct MlpDev {        // one loaded controller (device pointers)
+  const float* w1t;    // [38][h1]  W1 transposed
+  const float* b1;     // [h1]
+  const float* w2t;    // [h1][h2]  W2 transposed
+  const float* b2;     // [h2]
+  const float* w3;     // [2][h2]
+  const float* b3;     // [2]
+  int h1, h2, activation, output;
+};
+struct MlpLaunch {
+  const MlpDev* table;         // [MLP_MAX_CTRL]
+  const float* obs;            // [E][C][38]
+  float* act;                  // [E][C][2]
+  int env0, nenv, C;
+  int slot_id[MLP_MAX_CARS];   // blockIdx.y -> car slot c | controller id << 8
+};
+// tanhf as a call: inlined, its divergent branch (small / large |x|) cuts the unrolled activation loops into 16 (T1 + T2)
+// blocks, the accumulators are copied out of the AGPRs wholesale and the 256-wide nets spill (52 dwords at <8, 8>, 134
+// VGPRs at <2, 2>); called, <2, 2> holds 54 VGPRs + 32 AGPRs (5 waves per SIMD) and nothing spills
+__device__ __attribute__((noinline)) float mlp_tanh(float x) { return tanhf(x); }
+template <int ACT>
+__device__ __forceinline__ float mlp_act(float v) { return ACT == MLP_RELU ? fmaxf(v, 0.0f) : mlp_tanh(v); }
+template <int OUT>
+__device__ __forceinline__ f32x2 mlp_out(float mu0, float mu1) {
+  if (OUT == MLP_OUT_CLIP) return (f32x2){fminf(fmaxf(mu0, -1.0f), 1.0f), fminf(fmaxf(mu1, -1.0f), 1.0f)};
+  if (OUT == MLP_OUT_SQUASH) {
+    const float a0 = tanhf(mu0), a1 = tanhf(mu1);
+    return (f32x2){-1.0f + ((0.5f * (a0 + 1.0f)) * 2.0f), -1.0f + ((0.5f * (a1 + 1.0f)) * 2.0f)};
+  }
+  return (f32x2){mu0, mu1};
+}
+template <int T1, int T2, int ACT>
+__global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
+  constexpr int H1 = 32 * T1, H2 = 32 * T2;
+  __shared__ float s_b1[H1], s_b2[H2], s_w3[2 * H2];
+  const int c = L.slot_id[blockIdx.y] & 255;
+  const MlpDev W = L.table[L.slot_id[blockIdx.y] >> 8];
+  for (int i = threadIdx.x; i < H1; i += 64 * AM_WAVES) s_b1[i] = W.b1[i];
+  for (int i = threadIdx.x; i < H2; i += 64 * AM_WAVES) s_b2[i] = W.b2[i];
+  for (int i = threadIdx.x; i < 2 * H2; i += 64 * AM_WAVES) s_w3[i] = W.w3[i];
+  __syncthreads();
+  const int l = threadIdx.x & 63, r = l & 31, h = l >> 5;
+  const int tile = blockIdx.x * AM_WAVES + (threadIdx.x >> 6);
+  const int i0 = tile * 32;
+  if (i0 >= L.nenv) return;
+  const int i = i0 + r;
+  const size_t car = (size_t)(L.env0 + (i < L.nenv ? i : L.nenv - 1)) * L.C + c;
+  const float* xr = L.obs + car * ACT_OBS;
+  f32x16 hid[T1];   // layer-1 accumulators, then act(H1 + b1) in place: layer 2's B operands
+#pragma unroll
+  for (int t = 0; t < T1; ++t) hid[t] = (f32x16){};
+#pragma unroll
+  for (int s = 0; s < ACT_OBS / 2; ++s) {
+    const float b = xr[2 * s + h];
+    const float* w = W.w1t + (size_t)(2 * s + h) * H1 + r;
+#pragma unroll
+    for (int t = 0; t < T1; ++t) hid[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[32 * t], b, hid[t], 0, 0, 0);
+  }
+#pragma unroll
+  for (int t = 0; t < T1; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int u = 32 * t + (q & 3) + 8 * (q >> 2) + 4 * h;   // the 32x32 C/D map: register q of tile t on half h
+      hid[t][q] = mlp_act<ACT>(hid[t][q] + s_b1[u]);
+    }
+  f32x16 acc[T2];
+#pragma unroll
+  for (int o = 0; o < T2; ++o) acc[o] = (f32x16){};
+#pragma unroll
+  for (int t = 0; t < T1; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int u = 32 * t + (q & 3) + 8 * (q >> 2) + 4 * h;
+      const float* w = W.w2t + (size_t)u * H2 + r;
+      const float b = hid[t][q];
+#pragma unroll
+      for (int o = 0; o < T2; ++o) acc[o] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[32 * o], b, acc[o], 0, 0, 0);
+    }
+  // layer 3: partial sums over this lane's half of the hidden units, then the two halves of the observation added
+  float m0 = 0.0f, m1 = 0.0f;
+#pragma unroll
+  for (int t = 0; t < T2; ++t)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int u = 32 * t + (q & 3) + 8 * (q >> 2) + 4 * h;
+      const float v = mlp_act<ACT>(acc[t][q] + s_b2[u]);
+      m0 = fmaf(s_w3[u], v, m0);
+      m1 = fmaf(s_w3[H2 + u], v, m1);
+    }
+  m0 += __shfl_xor(m0, 32);
+  m1 += __shfl_xor(m1, 32);
+  if (h == 0 && i < L.nenv) {
+    const float mu0 = m0 + W.b3[0], mu1 = m1 + W.b3[1];
+    f32x2* out = (f32x2*)&L.act[2 * car];
+    switch (W.output) {   // wave-uniform
+      case MLP_OUT_SQUASH: *out = mlp_out<MLP_OUT_SQUASH>(mu0, mu1); break;
+      case MLP_OUT_CLIP: *out = mlp_out<MLP_OUT_CLIP>(mu0, mu1); break;
+      default: *out = mlp_out<MLP_OUT_RAW>(mu0, mu1); break;
+    }
+  }
+}
+
 #define AF_TILE 32
 __global__ void __launch_bounds__(256) actor_fp32_kernel(int N, const float* __restrict__ obs, float* __restrict__ act,
                                                          ActorF32 A) {

@@ -1793,6 +1793,20 @@ __global__ void policy_kernel(int N, int policy, uint64_t seed, int64_t step, co
   policy_car(policy, seed, step, n, obs, ctl, a0, a1);
   act[2 * n] = a0; act[2 * n + 1] = a1;
 }
+// Policy 4's built-in slots (nascar_set_car_controllers): cars [n0, n1) whose slot n % C holds NASCAR_CTRL_RULE /
+// _UNIFORM / _NOISY run policy_car as policy 1 / 0 / 3 (same key, same driver state: the results of policy_kernel for
+// that car); the slots of MLP controllers (code >= 0) are left to mlp_field_kernel, their driver state untouched.
+struct FieldCodes { signed char code[MLP_MAX_CARS]; };
+__global__ void field_policy_kernel(int n0, int n1, int C, FieldCodes F, uint64_t seed, int64_t step, const float* obs,
+                                    float* act, double* ctl) {
+  const int n = n0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= n1) return;
+  const int code = F.code[n % C];
+  if (code >= 0) return;
+  float a0, a1;
+  policy_car(code == NASCAR_CTRL_RULE ? 1 : code == NASCAR_CTRL_UNIFORM ? 0 : 3, seed, step, n, obs, ctl, a0, a1);
+  act[2 * n] = a0; act[2 * n + 1] = a1;
+}
 
 
 
@@ -3419,6 +3433,13 @@ struct NascarHandle {
   ActorDev actor{};
   void* d_actor32 = nullptr; ActorF32 actor32{};   // fp32 copies (nascar_set_actor_precision)
   int actor_fp32 = 1;   // default: reference precision
+  // per-car controllers (policy 4): the loaded MLPs (host image of the device table d_ctrl, one weight allocation
+  // each) and the slot -> controller table of nascar_set_car_controllers
+  std::vector<MlpDev> ctrl;
+  std::vector<void*> ctrl_mem;
+  MlpDev* d_ctrl = nullptr;
+  bool field_set = false;
+  int field[MLP_MAX_CARS];
   size_t max_lds = 0, max_sensor_lds = 0, max_sensor_groups_lds = 0;
   bool dirty_tracks = true;
   // sharded rollout (nascar_set_rollout_streams): shard s steps workgroups [nblocks*s/S, nblocks*(s+1)/S) on its
@@ -3582,6 +3603,8 @@ extern "C" void nascar_destroy(NascarHandle* h) {
   for (auto ev : h->ev_join) hipEventDestroy(ev);
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
   hipFree(h->d_ro_act);
+  for (void* p : h->ctrl_mem) hipFree(p);
+  hipFree(h->d_ctrl);
   hipFree(h->d_rt);
   delete h;
 }
@@ -4216,6 +4239,9 @@ extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed
                                   uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs,
                                   void* stream) {
   if (!h || !obs || !reward) return fail("null argument");
+  if (policy == 2 || policy == 4)
+    return fail("driven step: policy %d (MLP controllers) runs in launches of its own -- use nascar_policy_actions + nascar_step "
+                "or nascar_rollout", policy);
   if (policy != 0 && policy != 1 && policy != 3) return fail("driven step policy must be 0, 1 or 3 (got %d)", policy);
   return step_impl(h, nullptr, 0, policy, seed, step, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
 }
@@ -4310,18 +4336,23 @@ static int step_impl(NascarHandle* h, const void* actions, int32_t discrete, int
 // nascar_step_driven bit for bit (tests/test_gpu_rollout.py).
 // Policy 2 (the SAC actor): each shard runs the actor on its own cars' observations, then steps them -- the
 // cars of a shard are contiguous when the block map is the identity (one track, envs in workgroup order);
-// otherwise the rollout runs as one shard.
+// otherwise the rollout runs as one shard.  Policy 4 (the field of per-car controllers) likewise: each shard runs
+// launch_field on its own env range, then steps those envs.
 static void launch_actor(NascarHandle* h, int n, const float* obs, float* actions, void* stream);
+static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int64_t step, const float* obs, float* act,
+                        hipStream_t s);
 static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed, int64_t step0, int32_t steps, float* obs,
                            float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, int32_t traj,
                            hipStream_t stream) {
   S = std::max(1, std::min(S, h->nblocks));
   const bool rt = h->rt_on && auto_reset;
   if (h->rt_on) S = 1;   // random-track mode: the block map changes between steps, so no shard owns a fixed set of envs
-  const bool actor = policy == 2;
+  const bool field = policy == 4;
+  const bool actor = policy == 2 || field;   // the actions come from a launch of their own, into d_ro_act
   if (actor) {
-    if (!h->d_actor) return fail("policy 2 needs an actor (nascar_set_actor)");
-    if ((uintptr_t)obs & 7) return fail("actor obs must be 8-byte aligned");
+    if (field && !h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
+    if (!field && !h->d_actor) return fail("policy 2 needs an actor (nascar_set_actor)");
+    if (!field && ((uintptr_t)obs & 7)) return fail("actor obs must be 8-byte aligned");
     if (!h->map_identity) S = 1;
     if (!h->d_ro_act) HIPCHK(hipMalloc(&h->d_ro_act, sizeof(float) * 2 * (size_t)h->N));
   }
@@ -4364,7 +4395,10 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
           if (actor && ph == 0) {
             const size_t c0 = S == 1 ? 0 : (size_t)b0 * h->epb * h->C;
             const size_t c1 = S == 1 ? NC : std::min((size_t)b1 * h->epb, E) * h->C;
-            if (c1 > c0) launch_actor(h, (int)(c1 - c0), o_in + c0 * 38, h->d_ro_act + c0 * 2, shard_stream(s));
+            if (field) {
+              if (launch_field(h, (int)(c0 / h->C), (int)((c1 - c0) / h->C), seed, step0 + k, o_in, h->d_ro_act, shard_stream(s)))
+                return -1;
+            } else if (c1 > c0) launch_actor(h, (int)(c1 - c0), o_in + c0 * 38, h->d_ro_act + c0 * 2, shard_stream(s));
             HIPCHK(hipGetLastError());
           }
           if (launch_step_range(h, P, b1 - b0, actor ? h->d_ro_act : nullptr, 0, actor ? -1 : policy, seed, step0 + k,
@@ -4499,8 +4533,11 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
                               float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, int32_t traj,
                               void* stream) {
   if (!h || !obs || !reward) return fail("null argument");
-  if (policy < 0 || policy > 3) return fail("rollout policy must be 0, 1, 2 or 3 (got %d)", policy);
+  if (policy < 0 || policy > 4) return fail("rollout policy must be 0, 1, 2, 3 or 4 (got %d)", policy);
   if (policy == 2 && h->ro_streams == 0) return fail("the fused rollout kernel has no actor (policy 2): use the sharded rollout");
+  if (policy == 4 && h->ro_streams == 0)
+    return fail("the fused rollout kernel has no controllers (policy 4): use the sharded rollout (rollout streams >= 1)");
+  if (policy == 4 && !h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
   if (h->rt_on && h->ro_streams == 0)
     return fail("random-track mode needs the sharded rollout (rollout streams >= 1): the fused kernel keeps one block map");
   if (traj & ~(NASCAR_TRAJ_RECORDS | NASCAR_TRAJ_OBS)) return fail("unknown trajectory flags 0x%x", traj);
@@ -4510,7 +4547,7 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
   if (steps == 0) return 0;
   h->pristine = false;
   if (prepare(h, (hipStream_t)stream)) return -1;
-  if (h->ro_pipe > 0 && policy != 2 && !h->rt_on && !h->car_contact && !(traj & NASCAR_TRAJ_OBS))
+  if (h->ro_pipe > 0 && policy != 2 && policy != 4 && !h->rt_on && !h->car_contact && !(traj & NASCAR_TRAJ_OBS))
     return rollout_pipe(h, policy, seed, step0, steps, obs, reward, car_flags, env_flags, auto_reset, traj,
                         (hipStream_t)stream);
   if (h->ro_streams > 0)
@@ -4663,11 +4700,18 @@ extern "C" int nascar_set_state(NascarHandle* h, const void* src, void* stream) 
 }
 
 static void launch_actor(NascarHandle* h, int n, const float* obs, float* actions, void* stream);
+static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int64_t step, const float* obs, float* act,
+                        hipStream_t s);
 extern "C" int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, const float* obs,
                                      float* actions, void* stream) {
   if (!h || !actions) return fail("null argument");
-  if (policy < 0 || policy > 3) return fail("unknown policy %d", policy);
+  if (policy < 0 || policy > 4) return fail("unknown policy %d", policy);
   if (policy >= 1 && !obs) return fail("policy %d needs obs", policy);
+  if (policy == 4) {
+    if (!h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
+    if ((uintptr_t)actions & 7) return fail("field actions must be 8-byte aligned");
+    return launch_field(h, 0, h->E, seed, step, obs, actions, (hipStream_t)stream);
+  }
   if (policy == 2) {
     if (!h->d_actor) return fail("policy 2 needs an actor (nascar_set_actor)");
     if (((uintptr_t)obs | (uintptr_t)actions) & 7) return fail("actor obs/actions must be 8-byte aligned");
@@ -4805,6 +4849,145 @@ extern "C" int nascar_actor_forward(NascarHandle* h, const float* obs, int32_t n
   if (((uintptr_t)obs | (uintptr_t)actions) & 7) return fail("actor obs/actions must be 8-byte aligned");
   if (n == 0) return 0;
   launch_actor(h, n, obs, actions, stream);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------ per-car controllers (policy 4; nascar_actor.h)
+static bool mlp_shape_ok(int h1, int h2) {
+#define X(A, B) if (h1 == 32 * (A) && h2 == 32 * (B)) return true;
+  MLP_SHAPES(X)
+#undef X
+  return false;
+}
+extern "C" int nascar_check_controller(const NascarMlp* m) {
+  if (!m) return fail("null argument");
+  if (m->obs_dim != ACT_OBS || m->act_dim != ACT_OUT || !mlp_shape_ok(m->h1, m->h2))
+    return fail("controller shape %d -> %d -> %d -> %d unsupported: need obs 38, 2 actions and hidden layers 256-256, 256-128, "
+                "256-32, 128-128, 64-64 or 32-256 (the SB3 checkpoints the reference ships; TD3's [400, 300] is not among them)",
+                m->obs_dim, m->h1, m->h2, m->act_dim);
+  if (m->activation != MLP_RELU && m->activation != MLP_TANH)
+    return fail("controller activation must be 0 (ReLU) or 1 (Tanh), got %d", m->activation);
+  if (m->output != MLP_OUT_RAW && m->output != MLP_OUT_CLIP && m->output != MLP_OUT_SQUASH)
+    return fail("controller output must be 0 (raw), 1 (clip) or 2 (squash), got %d", m->output);
+  return 0;
+}
+extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
+  if (!h || !m) return fail("null argument");
+  if (nascar_check_controller(m)) return -1;
+  if (!m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3) return fail("null controller weights");
+  if ((int)h->ctrl.size() >= MLP_MAX_CTRL) return fail("at most %d controllers per handle", MLP_MAX_CTRL);
+  const int H1 = m->h1, H2 = m->h2;
+  // one allocation: W1^T [38][h1], b1, W2^T [h1][h2], b2, W3 [2][h2], b3 (the transposes give mlp_field_kernel's A
+  // operands coalesced rows)
+  std::vector<float> f((size_t)ACT_OBS * H1 + H1 + (size_t)H1 * H2 + H2 + 2 * (size_t)H2 + 2);
+  float* p = f.data();
+  float* w1t = p; p += (size_t)ACT_OBS * H1;
+  float* b1 = p; p += H1;
+  float* w2t = p; p += (size_t)H1 * H2;
+  float* b2 = p; p += H2;
+  float* w3 = p; p += 2 * (size_t)H2;
+  float* b3 = p;
+  for (int o = 0; o < H1; ++o)
+    for (int i = 0; i < ACT_OBS; ++i) w1t[(size_t)i * H1 + o] = m->w1[(size_t)o * ACT_OBS + i];
+  for (int o = 0; o < H2; ++o)
+    for (int i = 0; i < H1; ++i) w2t[(size_t)i * H2 + o] = m->w2[(size_t)o * H1 + i];
+  memcpy(b1, m->b1, 4 * (size_t)H1); memcpy(b2, m->b2, 4 * (size_t)H2); memcpy(w3, m->w3, 8 * (size_t)H2); memcpy(b3, m->b3, 8);
+  int cur = 0;
+  HIPCHK(hipGetDevice(&cur));
+  if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
+  void* d = nullptr;
+  hipError_t e = hipSuccess;
+  if (!h->d_ctrl) e = hipMalloc(&h->d_ctrl, sizeof(MlpDev) * MLP_MAX_CTRL);
+  if (e == hipSuccess) e = hipMalloc(&d, f.size() * 4);
+  if (e == hipSuccess) e = hipMemcpy(d, f.data(), f.size() * 4, hipMemcpyHostToDevice);
+  MlpDev D{};
+  if (e == hipSuccess) {
+    const float* d32 = (const float*)d;
+    D.w1t = d32 + (w1t - f.data()); D.b1 = d32 + (b1 - f.data()); D.w2t = d32 + (w2t - f.data());
+    D.b2 = d32 + (b2 - f.data()); D.w3 = d32 + (w3 - f.data()); D.b3 = d32 + (b3 - f.data());
+    D.h1 = H1; D.h2 = H2; D.activation = m->activation; D.output = m->output;
+    e = hipMemcpy(h->d_ctrl + h->ctrl.size(), &D, sizeof(MlpDev), hipMemcpyHostToDevice);
+  }
+  if (cur != h->cfg.device) hipSetDevice(cur);
+  if (e != hipSuccess) { hipFree(d); return fail("loading the controller failed: %s", hipGetErrorString(e)); }
+  h->ctrl.push_back(D);
+  h->ctrl_mem.push_back(d);
+  return (int)h->ctrl.size() - 1;
+}
+extern "C" int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl) {
+  if (!h) return fail("null argument");
+  if (!ctrl) { h->field_set = false; return 0; }
+  for (int c = 0; c < h->C; ++c)
+    if (ctrl[c] < NASCAR_CTRL_NOISY || ctrl[c] >= (int)h->ctrl.size())
+      return fail("car slot %d: unknown controller id %d (%d loaded with nascar_add_controller; built-in sources are -1 rule, "
+                  "-2 uniform, -3 noisy rule)", c, ctrl[c], (int)h->ctrl.size());
+  for (int c = 0; c < h->C; ++c) h->field[c] = ctrl[c];
+  h->field_set = true;
+  return 0;
+}
+// one launch of the instantiation for (T1, T2, activation); false if there is none (shapes are checked at load)
+static bool mlp_launch(int h1, int h2, int activation, dim3 grid, hipStream_t s, const MlpLaunch& L) {
+#define X(A, B)                                                                                                  \
+  if (h1 == 32 * (A) && h2 == 32 * (B)) {                                                                        \
+    if (activation == MLP_RELU) hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_RELU>), grid, dim3(64 * AM_WAVES), 0, s, L); \
+    else hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_TANH>), grid, dim3(64 * AM_WAVES), 0, s, L);              \
+    return true;                                                                                                 \
+  }
+  MLP_SHAPES(X)
+#undef X
+  return false;
+}
+// The field's actions for envs [env0, env0 + nenv) of obs / act ([E][C][38] / [E][C][2]): one mlp_field_kernel launch
+// per distinct (h1, h2, activation) among the table's controllers (all their slots in the launch's grid y), then one
+// field_policy_kernel launch for the built-in slots -- bounded by the instantiations, not by the controllers loaded.
+static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int64_t step, const float* obs, float* act,
+                        hipStream_t s) {
+  if (nenv <= 0) return 0;
+  const int C = h->C;
+  const int gx = ((nenv + 31) / 32 + AM_WAVES - 1) / AM_WAVES;
+  bool done[MLP_MAX_CARS] = {};
+  bool builtin = false;
+  for (int c = 0; c < C; ++c) {
+    if (h->field[c] < 0) { builtin = true; continue; }
+    if (done[c]) continue;
+    const MlpDev& K = h->ctrl[h->field[c]];
+    MlpLaunch L{};
+    L.table = h->d_ctrl; L.obs = obs; L.act = act; L.env0 = env0; L.nenv = nenv; L.C = C;
+    int ns = 0;
+    for (int d = c; d < C; ++d) {
+      if (h->field[d] < 0 || done[d]) continue;
+      const MlpDev& D = h->ctrl[h->field[d]];
+      if (D.h1 != K.h1 || D.h2 != K.h2 || D.activation != K.activation) continue;
+      L.slot_id[ns++] = d | (h->field[d] << 8);
+      done[d] = true;
+    }
+    if (!mlp_launch(K.h1, K.h2, K.activation, dim3(gx, ns), s, L))
+      return fail("no kernel for controller shape %d-%d", K.h1, K.h2);
+    HIPCHK(hipGetLastError());
+  }
+  if (builtin) {
+    FieldCodes F{};
+    for (int c = 0; c < C; ++c) F.code[c] = (signed char)std::max(h->field[c], -4);
+    const int n0 = env0 * C, n1 = (env0 + nenv) * C;
+    hipLaunchKernelGGL(field_policy_kernel, dim3((n1 - n0 + 255) / 256), dim3(256), 0, s, n0, n1, C, F, seed, step, obs, act,
+                       h->d_ctl);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}
+extern "C" int nascar_controller_forward(NascarHandle* h, int32_t id, const float* obs, int32_t n, float* actions,
+                                         void* stream) {
+  if (!h || !obs || !actions || n < 0) return fail("bad argument");
+  if (id < 0 || id >= (int)h->ctrl.size()) return fail("unknown controller id %d (%d loaded)", id, (int)h->ctrl.size());
+  if ((uintptr_t)actions & 7) return fail("controller actions must be 8-byte aligned");
+  if (n == 0) return 0;
+  const MlpDev& K = h->ctrl[id];
+  MlpLaunch L{};   // a flat batch: n envs of one car slot
+  L.table = h->d_ctrl; L.obs = obs; L.act = actions; L.env0 = 0; L.nenv = n; L.C = 1;
+  L.slot_id[0] = id << 8;
+  if (!mlp_launch(K.h1, K.h2, K.activation, dim3(((n + 31) / 32 + AM_WAVES - 1) / AM_WAVES, 1), (hipStream_t)stream, L))
+    return fail("no kernel for controller shape %d-%d", K.h1, K.h2);
   HIPCHK(hipGetLastError());
   return 0;
 }
