@@ -713,9 +713,13 @@ __device__ inline void contact_apply(Car& c, int ci, const LWall* W, const ManiR
 // Per-car Box2D work whose size varies by car (a car's TOI pairs) is listed per lane and computed by every
 // present lane of the wave, so a wave's time follows its total work rather than its busiest car.  (The same
 // scheme for b2World::Collide's manifolds was parity-green but measured neutral: 118.5 vs 118.8 us.)
+#ifndef TOI_JOBCAP        // (test builds shrink the two caps so that small scenes cross them; any value >= 1)
 #define TOI_JOBCAP 64     // b2TimeOfImpact pairs per compute round per wave (more pairs: further rounds)
+#endif
 struct ToiWaveLDS { float4 sw0[64], sw1[64]; int2 job[TOI_JOBCAP]; float res[TOI_JOBCAP]; };
+#ifndef MANI_JOBCAP
 #define MANI_JOBCAP 32    // event manifolds per wave and scan computed cooperatively (the rest by their owners)
+#endif
 struct ManiWaveLDS { float4 xf[64]; int2 job[MANI_JOBCAP]; ManiRes res[MANI_JOBCAP]; };
 #define BP_JOBCAP 128     // broadphase candidate tests per wave and round
 struct BpWaveLDS { float4 fat[64]; int2 job[BP_JOBCAP]; unsigned int hit[64][2]; };

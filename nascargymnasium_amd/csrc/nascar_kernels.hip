@@ -950,6 +950,9 @@ __device__ inline void car_reset(const Params& P, Car& c, int n, bool fresh, con
     find_new_contacts(c, S);
     c.bank = 0.0;
   } else {       // CarPhysics.reset_car + Car.reset (src/car_physics.py:550-571, src/car.py:1027-1058)
+    // the error flag is per episode: a pair dropped at MAXC earlier lay where the car was, and the list's stale pairs
+    // go at the next Collide; the pairs found at the start pose below raise it again if the stale ones leave no room
+    c.overflow = 0;
     set_transform(c, S, p, c.a);
     set_transform(c, S, c.xf.p, a);
     set_transform(c, S, p, c.a);

@@ -970,8 +970,9 @@ static void island_solve_toi(oworld *w, const owalls *W, const olistener *L, con
 static void solve_toi(oworld *w, const owalls *W, const olistener *L, float dt, int velIters) {
     opoly pa; car_poly(&pa);
     w->alpha0 = 0.0f;
+    w->toi_touching1 = w->toi_event_nct1 = w->toi_events = w->toi_max_island = 0;   /* statistics only */
     for (int i = 0; i < w->nct; ++i) { w->ct[i].flags &= ~(OC_TOI | OC_ISLAND); w->ct[i].toiCount = 0; w->ct[i].toi = 1.0f; }
-    for (;;) {
+    for (int pass = 0;; ++pass) {
         int minC = -1; float minAlpha = 1.0f;
         for (int i = 0; i < w->nct; ++i) {
             ocontact *c = &w->ct[i];
@@ -990,10 +991,13 @@ static void solve_toi(oworld *w, const owalls *W, const olistener *L, float dt, 
                 if (state == TOI_TOUCHING) alpha = fmin_b2(alpha0 + (1.0f - alpha0) * beta, 1.0f);
                 else alpha = 1.0f;
                 c->toi = alpha; c->flags |= OC_TOI;
+                if (pass == 0 && state == TOI_TOUCHING && alpha < 1.0f) ++w->toi_touching1;
             }
             if (alpha < minAlpha) { minC = i; minAlpha = alpha; }
         }
         if (minC < 0 || 1.0f - 10.0f * FLT_EPSILON < minAlpha) break;
+        ++w->toi_events;
+        if (pass == 0) w->toi_event_nct1 = w->nct;
         /* advance the car (walls are static: b2Body::Advance is a no-op on them) */
         ov2 bc0 = w->c0, bc = w->c; float ba0 = w->a0, ba = w->a, balpha0 = w->alpha0;
         {
@@ -1029,6 +1033,7 @@ static void solve_toi(oworld *w, const owalls *W, const olistener *L, float dt, 
             cidx[n++] = i;
         }
         float subdt = (1.0f - minAlpha) * dt;
+        if (n > w->toi_max_island) w->toi_max_island = n;
         island_solve_toi(w, W, L, cidx, n, subdt, velIters);
         sync_fixtures(w);
         for (int i = 0; i < w->nct; ++i) w->ct[i].flags &= ~(OC_TOI | OC_ISLAND);

@@ -62,6 +62,10 @@ typedef struct {
     /* contact list, index 0 == head of b2World::m_contactList */
     ocontact ct[OB_MAXC]; int nct; int overflow;
     float inv_dt0;
+    /* SolveTOI statistics of the last step (scene-coverage tests only; nothing computed reads them):
+       first-pass b2TimeOfImpact calls that gave TOUCHING with alpha < 1, nct at the first pass's event (0 if it
+       ended without one), events, largest TOI island */
+    int toi_touching1, toi_event_nct1, toi_events, toi_max_island;
 } oworld;
 
 /* contact-listener callbacks (src/car_physics.py:693-864), implemented by the env */

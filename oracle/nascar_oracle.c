@@ -1003,6 +1003,12 @@ EXPORT void or_car_info(void *h, int idx, double *o) {
     o[42] = c->cum_reward_info;
     o[43] = (double)sqrtf(c->w.v.x * c->w.v.x + c->w.v.y * c->w.v.y);   /* car_speed_ms */
 }
+/* SolveTOI statistics of the car's last step (b2_oracle.h oworld): toi_touching1, toi_event_nct1, toi_events,
+   toi_max_island -- what a scene exercises, for the coverage tests (tests/crowded.py) */
+EXPORT void or_car_toi_stats(void *h, int idx, int32_t out[4]) {
+    oenv *e = h; const oworld *w = &e->car[idx].w;
+    out[0] = w->toi_touching1; out[1] = w->toi_event_nct1; out[2] = w->toi_events; out[3] = w->toi_max_island;
+}
 /* unit hooks */
 EXPORT float or_sinf(float x) { return ob_sinf(x); }
 EXPORT float or_cosf(float x) { return ob_cosf(x); }

@@ -48,6 +48,7 @@ def lib():
         L.or_step.argtypes = [vp, f32p]
         L.or_outputs.argtypes = [vp, f32p, f32p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)]
         L.or_car_info.argtypes = [vp, ctypes.c_int, f64p]
+        L.or_car_toi_stats.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]
         L.or_sinf.restype = ctypes.c_float
         L.or_sinf.argtypes = [ctypes.c_float]
         L.or_cosf.restype = ctypes.c_float
@@ -129,6 +130,12 @@ class OracleEnv:
         o = np.zeros(len(INFO_FIELDS), np.float64)
         self.L.or_car_info(self.h, idx, _p(o, ctypes.c_double))
         return dict(zip(INFO_FIELDS, o.tolist()))
+
+    def car_toi_stats(self, idx):
+        """SolveTOI statistics of car idx's last step: (toi_touching1, toi_event_nct1, toi_events, toi_max_island)"""
+        o = np.zeros(4, np.int32)
+        self.L.or_car_toi_stats(self.h, idx, _p(o, ctypes.c_int32))
+        return o
 
 
 class OracleGroups:
