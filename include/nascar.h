@@ -312,6 +312,18 @@ int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl);
  * (device pointers, n floats).  Parity tests compare it with the host libm. */
 int nascar_debug_sincosf(const float* x, float* s, float* c, int32_t n, void* stream);
 
+/* Test hooks: the Box2D step's primitives on caller-given cases, one lane per case (device pointers).
+ * nascar_debug_toi: b2TimeOfImpact of a car sweep against a static wall box and the exact TOI cull's decision on the
+ *   same pair.  cases [n][12] float32: c0.x c0.y c.x c.y a0 a alpha0 | wall x y angle hx hy.  beta [n] float32 and
+ *   state [n] int32 are b2TOIOutput's t and state (1 failed, 2 overlapped, 3 touching, 4 separated); far [n] int32 is
+ *   1 where the step would skip the call.
+ * nascar_debug_collide: b2CollidePolygons of the car box at a pose against a wall box.  cases [n][8] float32:
+ *   x y angle | wall x y angle hx hy.  out [n][12] 32-bit words: word 0 = stage | point count << 2 | type << 4
+ *   (stage 0: only the point count was written, 1: + type, 2: + everything else), then local normal x y, local point
+ *   x y, point 0 x y id, point 1 x y id, 0. */
+int nascar_debug_toi(const float* cases, int32_t n, float* beta, int32_t* state, int32_t* far, void* stream);
+int nascar_debug_collide(const float* cases, int32_t n, float* out, void* stream);
+
 /* Test hook: sensors only.  poses: device float32 [E*C*3] (x, y, angle) per car, written into the sensor
  * hand-off; impl 1 = beam-list ray kernel (the step's default), 0 = wall-group kernel; writes the 16
  * DistanceSensor values obs[n*38 + 22 .. 37] (src/distance_sensor.py:71-117, src/car_env.py:946). */

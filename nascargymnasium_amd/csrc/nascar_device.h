@@ -1841,18 +1841,23 @@ __device__ __forceinline__ bool toi_far(const Car& c, const Poly* pa, const LWal
 // wall re-scans its 2-5 contacts after each event: sequential on one lane before).  Same alphas, same
 // scan order, same minimum, so the results are Box2D's.
 // b2TimeOfImpact of the car's sweep against static wall wl -> alpha of SolveTOI (1 unless TOUCHING)
+// (toi_beta: b2TimeOfImpact's own output, beta and the state; the nascar_debug_toi test hook reads both)
+__device__ __forceinline__ float toi_beta(float4 s0, float4 s1, const LWall& wl, int* state, int* iters = nullptr,
+                                          unsigned long long* cyc = nullptr) {
+  Poly pa; make_box(&pa, CAR_HX, CAR_HY);
+  Poly pb; make_box(&pb, wl.hx, wl.hy);
+  Sweep sA; sA.c0 = V(s0.x, s0.y); sA.c = V(s0.z, s0.w); sA.a0 = s1.x; sA.a = s1.y; sA.alpha0 = s1.z;
+  Sweep sB; sB.c0 = V(wl.px, wl.py); sB.c = sB.c0; sB.a0 = wl.ang; sB.a = wl.ang; sB.alpha0 = 0.0f;
+  Rot qw; qw.s = wl.qs; qw.c = wl.qc;
+  return time_of_impact(state, &pa, sA, &pb, sB, 1.0f, qw, __float_as_uint(wl.ang), iters, cyc);
+}
 __device__ __forceinline__ float toi_alpha(float4 s0, float4 s1, const LWall& wl, int* iters = nullptr,
                                            unsigned long long* cyc = nullptr) {
 #ifdef NASCAR_KO_TOIJOBS
   return 1.0f;
 #endif
-  Poly pa; make_box(&pa, CAR_HX, CAR_HY);
-  Poly pb; make_box(&pb, wl.hx, wl.hy);
-  Sweep sA; sA.c0 = V(s0.x, s0.y); sA.c = V(s0.z, s0.w); sA.a0 = s1.x; sA.a = s1.y; sA.alpha0 = s1.z;
-  Sweep sB; sB.c0 = V(wl.px, wl.py); sB.c = sB.c0; sB.a0 = wl.ang; sB.a = wl.ang; sB.alpha0 = 0.0f;
   int state;
-  Rot qw; qw.s = wl.qs; qw.c = wl.qc;
-  const float beta = time_of_impact(&state, &pa, sA, &pb, sB, 1.0f, qw, __float_as_uint(wl.ang), iters, cyc);
+  const float beta = toi_beta(s0, s1, wl, &state, iters, cyc);
   return state == TOI_TOUCHING ? fminb(s1.z + (1.0f - s1.z) * beta, 1.0f) : 1.0f;
 }
 #ifndef TOI_COOP_MANI

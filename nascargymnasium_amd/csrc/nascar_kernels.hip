@@ -4733,6 +4733,43 @@ __global__ void sincos_kernel(const float* x, float* s, float* c, int n) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) glibc_sincosf(x[i], &s[i], &c[i]);
 }
+
+// ------------------------------------------------------------------ test hooks: Box2D primitives on caller-given cases
+// One lane per case, so the lanes of a wave take whatever paths their cases take.  Both hooks call the functions
+// solve_toi calls (toi_beta under toi_alpha, toi_far, contact_manifold), as this library compiles them.
+// A TOI case is 12 floats: the car's sweep c0.x c0.y c.x c.y a0 a alpha0, then the wall px py angle hx hy.
+__device__ __forceinline__ LWall debug_wall(const float* w) {
+  LWall wl;
+  const Rot q = rot_set(w[2]);
+  wl.px = w[0]; wl.py = w[1]; wl.qs = q.s; wl.qc = q.c; wl.hx = w[3]; wl.hy = w[4]; wl.ang = w[2]; wl.key = 0;
+  return wl;
+}
+__global__ void __launch_bounds__(128) debug_toi_kernel(const float* cases, int n, float* beta, int32_t* state, int32_t* far) {
+  const int i = blockIdx.x * 128 + threadIdx.x;
+  if (i >= n) return;
+  const float* k = cases + (size_t)i * 12;
+  const LWall wl = debug_wall(k + 7);
+  int st;
+  beta[i] = toi_beta(make_float4(k[0], k[1], k[2], k[3]), make_float4(k[4], k[5], k[6], 0.0f), wl, &st);
+  state[i] = st;
+  Car c;   // the fields toi_far reads
+  c.c0 = V(k[0], k[1]); c.c = V(k[2], k[3]); c.a0 = k[4]; c.a = k[5]; c.alpha0 = k[6];
+  c.xf.p = c.c; c.xf.q = rot_set(c.a);
+  Poly pa; make_box(&pa, CAR_HX, CAR_HY);
+  far[i] = toi_far(c, &pa, wl) ? 1 : 0;
+}
+// A manifold case is 8 floats: the car's x y angle, then the wall px py angle hx hy; out[i] is the raw ManiRes.
+__global__ void __launch_bounds__(128) debug_collide_kernel(const float* cases, int n, float* out) {
+  const int i = blockIdx.x * 128 + threadIdx.x;
+  if (i >= n) return;
+  const float* k = cases + (size_t)i * 8;
+  Xf xfA; xfA.p = V(k[0], k[1]); xfA.q = rot_set(k[2]);
+  const ManiRes r = contact_manifold(xfA, debug_wall(k + 3));
+  float* o = out + (size_t)i * 12;
+  o[0] = r.a.x; o[1] = r.a.y; o[2] = r.a.z; o[3] = r.a.w;
+  o[4] = r.b.x; o[5] = r.b.y; o[6] = r.b.z; o[7] = r.b.w;
+  o[8] = r.c.x; o[9] = r.c.y; o[10] = r.c.z; o[11] = r.c.w;
+}
 static uint16_t f32_to_bf16_rne(float f) {
   uint32_t u; memcpy(&u, &f, 4);
   if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (uint16_t)((u >> 16) | 0x40);   // quiet NaN
@@ -4998,6 +5035,20 @@ extern "C" int nascar_controller_forward(NascarHandle* h, int32_t id, const floa
 extern "C" int nascar_debug_sincosf(const float* x, float* s, float* c, int32_t n, void* stream) {
   if (!x || !s || !c || n < 0) return fail("bad argument");
   hipLaunchKernelGGL(sincos_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, s, c, n);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+extern "C" int nascar_debug_toi(const float* cases, int32_t n, float* beta, int32_t* state, int32_t* far, void* stream) {
+  if (!cases || !beta || !state || !far || n < 0) return fail("bad argument");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(debug_toi_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, cases, n, beta, state, far);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+extern "C" int nascar_debug_collide(const float* cases, int32_t n, float* out, void* stream) {
+  if (!cases || !out || n < 0) return fail("bad argument");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(debug_collide_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, cases, n, out);
   HIPCHK(hipGetLastError());
   return 0;
 }

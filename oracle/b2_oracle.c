@@ -1124,3 +1124,44 @@ int ob_query_on_wall(const owalls *W, double px, double py, double radius) {
     }
     return 0;
 }
+
+/* ---- primitives on caller-given cases (tests/test_gpu_b2_prims.py): arrays in, arrays out, no world ---- */
+/* b2TimeOfImpact of a car sweep against a static wall box, built as solve_toi builds them.
+   case: c0x c0y cx cy a0 a alpha0 | wx wy wang whx why */
+__attribute__((visibility("default")))
+void or_toi(const float *cases, int n, float *beta, int32_t *state) {
+    opoly pa; car_poly(&pa);
+    for (int i = 0; i < n; ++i) {
+        const float *k = cases + (size_t)i * 12;
+        opoly pb; box(&pb, k[10], k[11]);
+        osweep sA = { V(k[0], k[1]), V(k[2], k[3]), k[4], k[5], k[6] };
+        osweep sB = { V(k[7], k[8]), V(k[7], k[8]), k[9], k[9], 0.0f };
+        int st;
+        beta[i] = time_of_impact(&st, &pa, &sA, &pb, &sB, 1.0f);
+        state[i] = st;
+    }
+}
+/* b2CollidePolygons of the car box against a wall box on a manifold seeded with sentinels (type -1, localNormal.x
+   the NaN 0x7fc0dead, the rest 0), so that the fields it leaves unwritten past an early exit can be told.
+   case: x y angle | wx wy wang whx why; out: type, pointCount, localNormal, localPoint, points' localPoint, ids (bits) */
+__attribute__((visibility("default")))
+void or_collide(const float *cases, int n, float *out) {
+    opoly pa; car_poly(&pa);
+    for (int i = 0; i < n; ++i) {
+        const float *k = cases + (size_t)i * 8;
+        float *o = out + (size_t)i * 12;
+        opoly pb; box(&pb, k[6], k[7]);
+        oxf xfA, xfB;
+        xfA.p = V(k[0], k[1]); ob_rot_set(&xfA.q, k[2]);
+        xfB.p = V(k[3], k[4]); ob_rot_set(&xfB.q, k[5]);
+        omanifold m; memset(&m, 0, sizeof(m));
+        const uint32_t unset = 0x7fc0deadu;
+        m.type = -1; memcpy(&m.localNormal.x, &unset, 4);
+        collide_polygons(&m, &pa, xfA, &pb, xfB);
+        o[0] = (float)m.type; o[1] = (float)m.pointCount;
+        o[2] = m.localNormal.x; o[3] = m.localNormal.y; o[4] = m.localPoint.x; o[5] = m.localPoint.y;
+        o[6] = m.pts[0].localPoint.x; o[7] = m.pts[0].localPoint.y;
+        o[8] = m.pts[1].localPoint.x; o[9] = m.pts[1].localPoint.y;
+        memcpy(&o[10], &m.pts[0].id, 4); memcpy(&o[11], &m.pts[1].id, 4);
+    }
+}

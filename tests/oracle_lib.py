@@ -56,8 +56,31 @@ def lib():
         L.or_raycast.restype = ctypes.c_float
         L.or_raycast.argtypes = [vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]
         L.or_set_body.argtypes = [vp, ctypes.c_int] + [ctypes.c_float] * 6
+        L.or_toi.restype = None
+        L.or_toi.argtypes = [f32p, ctypes.c_int, f32p, ctypes.POINTER(ctypes.c_int32)]
+        L.or_collide.restype = None
+        L.or_collide.argtypes = [f32p, ctypes.c_int, f32p]
         _lib = L
     return _lib
+
+
+def toi(cases):
+    """or_toi on cases [n, 12] float32 (c0x c0y cx cy a0 a alpha0 | wx wy wang whx why): b2TimeOfImpact's
+    (beta [n] float32, state [n] int32)."""
+    cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 12)
+    beta = np.zeros(len(cases), np.float32)
+    state = np.zeros(len(cases), np.int32)
+    lib().or_toi(_p(cases, ctypes.c_float), len(cases), _p(beta, ctypes.c_float), _p(state, ctypes.c_int32))
+    return beta, state
+
+
+def collide(cases):
+    """or_collide on cases [n, 8] float32 (x y angle | wx wy wang whx why): [n, 12] float32 -- type, point count,
+    local normal, local point, the two points' local coordinates, their ids as bit patterns."""
+    cases = np.ascontiguousarray(cases, np.float32).reshape(-1, 8)
+    out = np.zeros((len(cases), 12), np.float32)
+    lib().or_collide(_p(cases, ctypes.c_float), len(cases), _p(out, ctypes.c_float))
+    return out
 
 
 def _p(a, t):

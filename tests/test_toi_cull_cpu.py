@@ -10,8 +10,7 @@ at the steady state: 0 of ~30 k per step TOUCHING)
 """
 import numpy as np
 
-CAR_HX, CAR_HY = 5.042 / 2.0, 1.996 / 2.0
-R_CAR = 2.80389
+from b2_cases import CAR_HX, CAR_HY, bounds   # the float64 restatement of the two bounds (shared with the case tests)
 
 
 def rot(a):
@@ -58,29 +57,6 @@ def box_distance(P, Q):
 
 def ext(u, ax, ay, hx, hy):
     return hx * np.abs((u * ax).sum(-1)) + hy * np.abs((u * ay).sum(-1))
-
-
-def bounds(c0, a0, c1, a1, w, wa, whx, why):
-    """(first-order bound, second-order bound) as toi_far / toi_far_rot2 compute them (float64 here)."""
-    q1 = rot(a1)
-    cx1, cy1 = q1, np.stack([-q1[:, 1], q1[:, 0]], -1)
-    q0 = rot(a0)
-    cx0, cy0 = q0, np.stack([-q0[:, 1], q0[:, 0]], -1)
-    wx = rot(wa)
-    wy = np.stack([-wx[:, 1], wx[:, 0]], -1)
-    d1, d0, dc = c1 - w, c0 - w, c1 - c0
-    b1 = np.full(len(a0), -np.inf)
-    b2 = np.full(len(a0), -np.inf)
-    for u in (wx, wy, cx1, cy1):
-        s1, s0 = (u * d1).sum(-1), (u * d0).sum(-1)
-        we = ext(u, wx, wy, whx, why)
-        g1 = np.abs(s1) - ext(u, cx1, cy1, CAR_HX, CAR_HY) - we
-        away = np.where(s1 >= 0, (u * dc).sum(-1), -(u * dc).sum(-1))
-        b1 = np.maximum(b1, g1 - np.maximum(0.0, away))
-        g0 = np.where(s1 >= 0, s0, -s0) - ext(u, cx0, cy0, CAR_HX, CAR_HY) - we
-        b2 = np.maximum(b2, np.minimum(g0, g1))
-    da = np.abs(a1 - a0)
-    return b1 - da * R_CAR, b2 - da * da * (R_CAR / 8.0)
 
 
 def test_toi_cull_bounds_below_swept_distance():

@@ -6,7 +6,8 @@ The jobs come from a -DNASCAR_PROFILE -DNASCAR_TOI_CAPTURE build (tools/phase_pr
 (variants of nascar_device.h's toi_alpha built with different -D flags) and each (lanes, workgroups) setting it prints
 s_memtime cycles per round -- lanes = 1: one call at a time, a lone TOI chain as in the slowest wave's scans -- split by
 outcome (alpha < 1: TOUCHING, the event-producing calls), and checks that every variant's alphas equal the first's
-bit for bit.
+bit for bit.  (That the product's alphas are Box2D's is the suite's business: tests/test_gpu_b2_prims.py compares
+time_of_impact with the oracle's on these jobs and on hand-made cases.)
 """
 import argparse
 import ctypes
