@@ -312,6 +312,11 @@ int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl);
  * (device pointers, n floats).  Parity tests compare it with the host libm. */
 int nascar_debug_sincosf(const float* x, float* s, float* c, int32_t n, void* stream);
 
+/* Test hook: the float64 library functions of the vehicle model, as the step kernels' build compiles them (device
+ * pointers, n doubles).  fn 0: exp(-2 x); 1: atan2(|x|, y); 2: tan(x); 3: sqrt(x*x + y*y) as the model writes Python's
+ * (x**2 + y**2) ** 0.5; 4: x*x as it writes x ** 2.  y may be null for fn 0, 2 and 4. */
+int nascar_debug_f64math(const double* x, const double* y, double* out, int32_t n, int32_t fn, void* stream);
+
 /* Test hooks: the Box2D step's primitives on caller-given cases, one lane per case (device pointers).
  * nascar_debug_toi: b2TimeOfImpact of a car sweep against a static wall box and the exact TOI cull's decision on the
  *   same pair.  cases [n][12] float32: c0.x c0.y c.x c.y a0 a alpha0 | wall x y angle hx hy.  beta [n] float32 and

@@ -146,6 +146,8 @@ def lib():
     L.nascar_set_step_events.restype = ctypes.c_int
     L.nascar_debug_sincosf.argtypes = [vp, vp, vp, i32, vp]
     L.nascar_debug_sincosf.restype = ctypes.c_int
+    L.nascar_debug_f64math.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.nascar_debug_f64math.restype = ctypes.c_int
     L.nascar_debug_toi.argtypes = [vp, i32, vp, vp, vp, vp]
     L.nascar_debug_toi.restype = ctypes.c_int
     L.nascar_debug_collide.argtypes = [vp, i32, vp, vp]
@@ -180,7 +182,7 @@ EXPORTED = ["nascar_create", "nascar_destroy", "nascar_last_error", "nascar_add_
             "nascar_reset", "nascar_step", "nascar_step_driven", "nascar_rollout", "nascar_get_info", "nascar_set_perf_history", "nascar_set_car_contact", "nascar_set_rollout_streams", "nascar_get_rollout_streams", "nascar_set_rollout_pipe", "nascar_rollout_pipe_status", "nascar_set_envs_per_block", "nascar_get_envs_per_block", "nascar_set_sensor_lanes", "nascar_set_sensor_block", "nascar_set_beam_cell", "nascar_set_fused_logic", "nascar_get_fused_logic", "nascar_state_bytes", "nascar_get_state",
             "nascar_set_state", "nascar_policy_actions", "nascar_set_step_events", "nascar_set_actor", "nascar_set_actor_precision", "nascar_actor_forward",
             "nascar_check_controller", "nascar_add_controller", "nascar_controller_forward", "nascar_set_car_controllers",
-            "nascar_debug_sincosf", "nascar_debug_toi", "nascar_debug_collide", "nascar_debug_sensors", "nascar_track_draw", "nascar_set_random_tracks",
+            "nascar_debug_sincosf", "nascar_debug_f64math", "nascar_debug_toi", "nascar_debug_collide", "nascar_debug_sensors", "nascar_track_draw", "nascar_set_random_tracks",
             "nascar_get_env_tracks", "nascar_vec_post", "nascar_check_actions", "nascar_set_track_cache",
             "nascar_prebuild_track", "nascar_debug_block_map"]
 

@@ -4734,6 +4734,25 @@ __global__ void sincos_kernel(const float* x, float* s, float* c, int n) {
   if (i < n) glibc_sincosf(x[i], &s[i], &c[i]);
 }
 
+// ------------------------------------------------------------------ test hook: the vehicle model's float64 library calls
+// fn 0: exp(-2 x) (the engine force's blend), 1: atan2(|x|, y) (the slip angle), 2: tan(x) (the steering torque),
+// 3: PH(P2(x) + P2(y)) (the lateral force's magnitude), 4: P2(x) -- written as car_update_physics writes them and
+// compiled with this library's flags, so the test sees the functions the model calls
+__global__ void f64math_kernel(const double* x, const double* y, double* out, int n, int fn) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double a = x[i], b = y ? y[i] : 0.0;
+  double r;
+  switch (fn) {
+    case 0: r = exp(-2.0 * a); break;
+    case 1: r = atan2(fabs(a), b); break;
+    case 2: r = tan(a); break;
+    case 3: r = PH(P2(a) + P2(b)); break;
+    default: r = P2(a); break;
+  }
+  out[i] = r;
+}
+
 // ------------------------------------------------------------------ test hooks: Box2D primitives on caller-given cases
 // One lane per case, so the lanes of a wave take whatever paths their cases take.  Both hooks call the functions
 // solve_toi calls (toi_beta under toi_alpha, toi_far, contact_manifold), as this library compiles them.
@@ -5035,6 +5054,15 @@ extern "C" int nascar_controller_forward(NascarHandle* h, int32_t id, const floa
 extern "C" int nascar_debug_sincosf(const float* x, float* s, float* c, int32_t n, void* stream) {
   if (!x || !s || !c || n < 0) return fail("bad argument");
   hipLaunchKernelGGL(sincos_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, s, c, n);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+extern "C" int nascar_debug_f64math(const double* x, const double* y, double* out, int32_t n, int32_t fn, void* stream) {
+  if (!x || !out || n < 0) return fail("null argument");
+  if (fn < 0 || fn > 4) return fail("unknown function %d", fn);
+  if ((fn == 1 || fn == 3) && !y) return fail("function %d needs y", fn);
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(f64math_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, out, n, fn);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -789,6 +789,9 @@ static void env_reset(oenv *e, int env) {
         c->lt_crossed = 0; c->lt_has_pos = 0; c->lt_laps = 0; c->lt_dist = 0.0;
         c->disabled = 0; c->just_disabled = 0; c->cum_impact = 0.0;
         c->stuck_dur = 0.0; c->has_stuck_start = 0;
+        /* None in the reference after a reset; never read before they are set again.  Zero, as the device stores
+           them, so that a reset state compares field for field (or_get_car_full) */
+        c->lt_last = c->lt_best = 0.0; c->lt_px = c->lt_py = 0.0; c->stuck_sx = c->stuck_sy = 0.0; c->imp_at_obs = 0.0;
         c->prev_px = c->w.xf.p.x; c->prev_py = c->w.xf.p.y;
         c->back = c->prev_back = 0.0; c->first_step = 1; c->prev_laps = 0; c->cum_reward = 0.0f; c->cum_reward_info = 0.0f;
         c->prog_hist = track_progress(&e->trk, c->w.xf.p.x, c->w.xf.p.y);
@@ -1143,4 +1146,52 @@ EXPORT void or_set_env_full(void *h, int env, double sim_time, int created, int 
     oenv *e = h;
     e->sim_time[env] = sim_time; e->created[env] = created; e->pending[env] = pending;
     e->term_reason[env] = reason; e->terminated[env] = term; e->truncated[env] = trunc;
+}
+
+/* ================= state read-back (test infrastructure) ==========================
+ * The exact inverse of or_set_car_full / or_set_env_full: the car's state in the GPU arena's layout, so one step of
+ * the oracle can be compared with one step of the device field by field (tests/test_gpu_state_parity.py).
+ * lt_has_pos is reported in the device's encoding: bit 0 = a previous position is recorded, bit 1 = that position
+ * lies on the start line (the device caches LapTimer._is_on_start_line(previous_position), which this restatement
+ * re-evaluates from lt_px / lt_py at the next step). */
+EXPORT void or_get_car_full(void *h, int idx, double *f32v, double *f64v, int *i32v, double *acc20,
+                            int32_t *ct_words, int32_t *act_key, float *act_n) {
+    oenv *e = h; ocar *c = &e->car[idx]; const oworld *w = &c->w;
+    const double f[18] = { w->c.x, w->c.y, w->a, w->v.x, w->v.y, w->w, w->xf.q.s, w->xf.q.c, w->xf.p.x, w->xf.p.y,
+        w->sleepTime, w->inv_dt0, w->fat.lo.x, w->fat.lo.y, w->fat.hi.x, w->fat.hi.y, c->cum_reward, c->cum_reward_info };
+    memcpy(f32v, f, sizeof f);
+    const double d[36] = { c->rpm, c->pvx, c->pvy, c->lfm, c->slip, c->bank, c->load[0], c->load[1], c->load[2], c->load[3],
+        c->temp[0], c->temp[1], c->temp[2], c->temp[3], c->wear[0], c->wear[1], c->wear[2], c->wear[3], c->imp,
+        c->lt_start, c->lt_cur, c->lt_last, c->lt_best, c->lt_px, c->lt_py, c->lt_dist, c->cum_impact, c->stuck_dur,
+        c->stuck_sx, c->stuck_sy, c->prev_px, c->prev_py, c->prog_hist, c->back, c->prev_back, c->imp_at_obs };
+    memcpy(f64v, d, sizeof d);
+    int has_pos = 0;
+    if (c->lt_has_pos) has_pos = 1 | ((e->trk.startline >= 0 && on_startline(&e->trk, c->lt_px, c->lt_py)) ? 2 : 0);
+    const int v[17] = { w->awake, w->nct, w->overflow, c->acc_len, c->acc_head, c->imp_present, c->nact, c->lt_timing,
+        c->lt_has_last, c->lt_has_best, c->lt_crossed, has_pos, c->lt_laps, c->disabled, c->has_stuck_start,
+        c->first_step, c->prev_laps };
+    memcpy(i32v, v, sizeof v);
+    for (int s = 0; s < 10; ++s) { acc20[2 * s] = c->acc[s][0]; acc20[2 * s + 1] = c->acc[s][1]; }
+    for (int i = 0; i < GPU_MAXC; ++i) {
+        int32_t *q = ct_words + 20 * i;
+        const ocontact *o = &w->ct[i];
+        q[0] = o->wall; q[1] = o->flags; q[2] = o->m.type; q[3] = o->m.pointCount;
+        memcpy(&q[4], &o->m.localNormal.x, 4); memcpy(&q[5], &o->m.localNormal.y, 4);
+        memcpy(&q[6], &o->m.localPoint.x, 4); memcpy(&q[7], &o->m.localPoint.y, 4);
+        for (int p = 0; p < 2; ++p) {
+            int32_t *pp = q + 8 + 5 * p;
+            memcpy(&pp[0], &o->m.pts[p].localPoint.x, 4); memcpy(&pp[1], &o->m.pts[p].localPoint.y, 4);
+            memcpy(&pp[2], &o->m.pts[p].normalImpulse, 4); memcpy(&pp[3], &o->m.pts[p].tangentImpulse, 4);
+            memcpy(&pp[4], &o->m.pts[p].id, 4);
+        }
+        memcpy(&q[18], &o->toi, 4); q[19] = o->toiCount;
+    }
+    for (int i = 0; i < GPU_MAXC; ++i) { act_key[i] = c->act_key[i]; act_n[2 * i] = c->act_nx[i]; act_n[2 * i + 1] = c->act_ny[i]; }
+}
+/* out: simulated time; words: created, pending, reason, terminated, truncated */
+EXPORT void or_get_env_full(void *h, int env, double *sim_time, int *words) {
+    oenv *e = h;
+    *sim_time = e->sim_time[env];
+    words[0] = e->created[env]; words[1] = e->pending[env]; words[2] = e->term_reason[env];
+    words[3] = e->terminated[env]; words[4] = e->truncated[env];
 }

@@ -261,13 +261,15 @@ def gpu_arena(blob, E, C):
     return out
 
 
-def inject_gpu_state(orc, blob, E, C, envs):
+def inject_gpu_state(orc, blob, E, C, envs, wire=True):
     """Continue OracleEnv `orc` (len(envs) envs x C cars) from the GPU state `blob` of an E x C engine: oracle env i
     takes GPU env envs[i].  Returns the driver state rows (throttle_brake, steering, last_forward, speed_limit) of
-    the selected cars, to seed the host rule driver (tests/drivers.py) as the device one stands."""
+    the selected cars, to seed the host rule driver (tests/drivers.py) as the device one stands.  wire=False skips
+    the reset that wires the cars' worlds to the track: for an `orc` that was injected into (or reset) before."""
     A = gpu_arena(blob, E, C)
     L = orc.L
-    orc.reset()   # every car's world wired to the track (the injected state then overwrites its fields)
+    if wire:
+        orc.reset()   # every car's world wired to the track (the injected state then overwrites its fields)
     dp, ip, fp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
     L.or_set_car_full.argtypes = [ctypes.c_void_p, ctypes.c_int, dp, dp, ip, dp, ip, ip, fp]
     L.or_set_env_full.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double] + [ctypes.c_int] * 5
@@ -289,3 +291,77 @@ def inject_gpu_state(orc, blob, E, C, envs):
                               _p(key, ctypes.c_int32), _p(nn, ctypes.c_float))
             rows.append(A["ctl"][n])
     return np.array(rows)
+
+
+# ---------------------------------------------------------------- oracle -> GPU arena layout (state read-back)
+ARENA_SECTIONS = ("f32", "f64", "i32", "acc", "ct", "key", "n", "time", "ei32", "ctl")
+
+
+def arena_bytes(E, C):
+    """size of the nascar_get_state blob of an E x C engine (every section rounded up to 256 bytes)"""
+    from gpu_state import F32, F64, I32
+    N = E * C
+    sizes = [4 * len(F32) * N, 8 * len(F64) * N, 4 * len(I32) * N, 8 * 20 * N, 80 * GPU_MAXC * N, 4 * GPU_MAXC * N,
+             8 * GPU_MAXC * N, 8 * E, 4 * N_EI32 * E, 8 * 4 * N]
+    return sum(_a256(s) for s in sizes)
+
+
+def pack_arena(A, E, C):
+    """The inverse of gpu_arena: a fresh uint8 blob of an E x C engine holding the sections of `A` (any mapping with
+    gpu_arena's keys and shapes; a missing "ctl" is left zero).  gpu_arena returns views, so editing the sections of
+    gpu_arena(blob) in place edits a writable blob directly; pack_arena is for sections that come from elsewhere (the
+    oracle's read-back, car_full) or from a read-only blob."""
+    blob = np.zeros(arena_bytes(E, C), np.uint8)
+    V = gpu_arena(blob, E, C)
+    for k in ARENA_SECTIONS:
+        if k in A:
+            V[k][...] = np.asarray(A[k]).reshape(V[k].shape)
+    return blob
+
+
+def get_car_full(orc, idx):
+    """or_get_car_full of car idx: (f32 [18] float32, f64 [36], i32 [17], acc [20], ct [320] int32, key [16] int32,
+    n [32] float32) in the GPU arena's field order"""
+    from gpu_state import F32, F64, I32
+    L = orc.L
+    dp, ip, fp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+    L.or_get_car_full.argtypes = [ctypes.c_void_p, ctypes.c_int, dp, dp, ip, dp, ip, ip, fp]
+    f32 = np.zeros(len(F32), np.float64)
+    f64 = np.zeros(len(F64), np.float64)
+    i32 = np.zeros(len(I32), np.int32)
+    acc = np.zeros(20, np.float64)
+    ct = np.zeros(GPU_MAXC * 20, np.int32)
+    key = np.zeros(GPU_MAXC, np.int32)
+    nn = np.zeros(GPU_MAXC * 2, np.float32)
+    L.or_get_car_full(orc.h, idx, _p(f32, ctypes.c_double), _p(f64, ctypes.c_double), _p(i32, ctypes.c_int32),
+                      _p(acc, ctypes.c_double), _p(ct, ctypes.c_int32), _p(key, ctypes.c_int32), _p(nn, ctypes.c_float))
+    return f32.astype(np.float32), f64, i32, acc, ct, key, nn
+
+
+def get_env_full(orc, env):
+    """or_get_env_full: (simulated time, [created, pending, reason, terminated, truncated] int32)"""
+    L = orc.L
+    L.or_get_env_full.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                  ctypes.POINTER(ctypes.c_int32)]
+    t = ctypes.c_double(0.0)
+    w = np.zeros(N_EI32, np.int32)
+    L.or_get_env_full(orc.h, env, ctypes.byref(t), _p(w, ctypes.c_int32))
+    return t.value, w
+
+
+def oracle_arena(orc):
+    """The whole state of OracleEnv `orc` as the sections gpu_arena returns (fresh arrays; no "ctl": the oracle has
+    no driver state), so pack_arena(oracle_arena(orc), E, C) is the blob a device engine in that state would hold."""
+    from gpu_state import F32, F64, I32
+    E, C = orc.E, orc.C
+    N = E * C
+    A = dict(f32=np.zeros((len(F32), N), np.float32), f64=np.zeros((len(F64), N), np.float64),
+             i32=np.zeros((len(I32), N), np.int32), acc=np.zeros((20, N), np.float64),
+             ct=np.zeros((N, GPU_MAXC * 20), np.int32), key=np.zeros((N, GPU_MAXC), np.int32),
+             n=np.zeros((N, GPU_MAXC * 2), np.float32), time=np.zeros(E, np.float64), ei32=np.zeros((N_EI32, E), np.int32))
+    for n in range(N):
+        A["f32"][:, n], A["f64"][:, n], A["i32"][:, n], A["acc"][:, n], A["ct"][n], A["key"][n], A["n"][n] = \
+            get_car_full(orc, n)
+    for e in range(E):
+        A["time"][e], A["ei32"][:, e] = get_env_full(orc, e)
+    return A

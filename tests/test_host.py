@@ -55,7 +55,7 @@ def test_capi_library_exports_every_declared_symbol():
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
     hdr = open(os.path.join(ROOT, "include", "nascar.h")).read()
-    declared = set(re.findall(r"\b(nascar_[a-z_]+)\s*\(", hdr))
+    declared = set(re.findall(r"\b(nascar_[a-z0-9_]+)\s*\(", hdr))
     assert declared == set(_lib.EXPORTED)
     L = ctypes.CDLL(_lib.LIB_PATH)
     for sym in declared:
