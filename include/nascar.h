@@ -225,6 +225,24 @@ int nascar_get_info(NascarHandle* h, double* info, void* stream);
  * (reference behaviour); parity runs with 0.  Takes effect from the next reset (start grid) and step. */
 int nascar_set_car_contact(NascarHandle* h, int32_t enable);
 
+/* BUILD-ONLY EXTENSION, no reference counterpart (the reference's ray-cast callback drops every fixture that is not a
+ * track wall, src/distance_sensor.py:45-47: its cars live in separate worlds): enable != 0 makes the 16 distance
+ * sensors of a car see the other cars of its env.  Ray i of car n is the ray cast without the extension (same p1, same
+ * float32 end point); its hit fraction becomes the minimum of the wall fraction and b2PolygonShape::RayCast against
+ * the box of every other car of the env, taken from the poses the same sensor pass reads (the step's pose for obs and
+ * terminal_obs, the auto-reset pose for the reset envs' obs): centre the body origin, rotation b2Rot::Set of the
+ * float32 body angle, half extents of the car fixture, lower = 0 / upper = 1.  A ray that starts inside another
+ * car's box reports no hit from it; a car never tests itself; disabled cars stay visible.  The value reaches
+ * obs[22:38], terminal_obs[22:38], the rollout's obs trajectory and everything read from them; rewards, flags and
+ * termination do not read the sensors and stay the reference's.  Independent of nascar_set_car_contact (with contact
+ * off the cars are ghosts that are seen but not touched); not part of the state arena.  Default 0: every output is
+ * the one without the extension, bit for bit.  Takes effect from the next reset / step / rollout.
+ * Refused, with an error naming the combination, by reset / step / rollout in random-track mode and by the fused
+ * single-launch rollout (rollout streams 0); the pipelined rollout falls back to the streams schedule.
+ * nascar_get_car_visibility returns the current setting (-1 for a NULL handle). */
+int nascar_set_car_visibility(NascarHandle* h, int32_t enable);
+int nascar_get_car_visibility(NascarHandle* h);
+
 /* Car.velocity_history for Car.validate_performance (src/car.py:173, 384-386, 1060-1098): enable != 0 keeps
  * every car's speed after each step in a 600-sample window on the device (VH_RING x N float32, outside the
  * state arena, so snapshots do not carry it) and nascar_get_info reports perf_count / perf_max_speed /

@@ -81,8 +81,22 @@ class BatchedCarEnv:
 
     def set_car_contact(self, enable: bool = True):
         """BUILD-ONLY EXTENSION (no reference counterpart): cars of an env collide with each other (staggered start
-        grid, central impulses between overlapping closing car boxes).  Off by default; parity holds only when off."""
+        grid; after each Box2D step the env's touching car pairs are solved with b2CollidePolygons manifolds and
+        b2ContactSolver's sequential friction and normal impulses, see include/nascar.h).  Off by default; parity holds
+        only when off."""
         _lib.check(self.L.nascar_set_car_contact(self.h, int(bool(enable))))
+
+    def set_car_visibility(self, enable: bool = True):
+        """BUILD-ONLY EXTENSION (no reference counterpart): the 16 distance sensors of a car also see the other cars
+        of its env -- each ray's hit fraction is the minimum of the wall hit and b2PolygonShape::RayCast against the
+        other cars' boxes at the poses the same observation is taken from (include/nascar.h).  Independent of
+        set_car_contact; off by default, and off is bit-identical to the reference.  Not supported with random-track
+        mode or the fused single-launch rollout (`set_rollout_streams(0)`): those calls raise."""
+        _lib.check(self.L.nascar_set_car_visibility(self.h, int(bool(enable))))
+
+    @property
+    def car_visibility(self) -> bool:
+        return bool(self.L.nascar_get_car_visibility(self.h))
 
     def set_rollout_streams(self, streams: int = 4):
         """How `rollout` schedules its steps (identical results either way): streams >= 1 splits the envs into that

@@ -372,6 +372,15 @@ class CarEnv(BaseEnv):
     def set_state(self, blob):
         self._engine.set_state(blob)
 
+    def set_car_visibility(self, enable: bool = True):
+        """BUILD-ONLY EXTENSION (no reference counterpart; the constructor stays the reference's): the distance sensors
+        also see this env's other cars (BatchedCarEnv.set_car_visibility).  Off by default."""
+        self._engine.set_car_visibility(enable)
+
+    @property
+    def car_visibility(self) -> bool:
+        return self._engine.car_visibility
+
     def close(self):
         eng = getattr(self, "_engine", None)
         if eng is not None:

@@ -1060,7 +1060,9 @@ __device__ __forceinline__ unsigned seg_ray_mask(float ax, float ay, float bx, f
   return ((m << (lo & 15)) | (m >> (16 - (lo & 15)))) & 0xFFFFu;
 }
 
-template <int LPC>
+__device__ __forceinline__ float car_casts(const Params& P, int n, int pass, V2 p1, float p2x, float p2y, float dx, float dy,
+                                           float bi);
+template <int LPC, bool VIS = false>   // VIS: opponent-aware sensors (car_casts, below), after the walls
 #ifndef SENSOR_WPE
 #define SENSOR_WPE 6   // 80 VGPRs: all 5 464 waves of the 8192x10 bench resident at once (measured best of 4/5/6)
 #endif
@@ -1224,7 +1226,12 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SENS
 #pragma unroll
       for (int q = 0; q < RPL; ++q) {
         const int i = r * RPL + q;
-        const float val = sensor_value(__uint_as_float(best[i]));
+        float bi = __uint_as_float(best[i]);
+        if constexpr (VIS) {   // the env's other cars (each lane: its own rays, after every lane's walls)
+          const float px2 = p2s[2 * i], py2 = p2s[2 * i + 1];
+          bi = car_casts(P, n, pass, p1, px2, py2, (px2 - p1.x) * 0.004f, (py2 - p1.y) * 0.004f, bi);
+        }
+        const float val = sensor_value(bi);
         if (pass == 0) {
           if (mode & PM_A_OBS) obs[(size_t)n * 38 + 22 + i] = val;
           if (mode & PM_A_TERM) terminal_obs[(size_t)n * 38 + 22 + i] = val;
@@ -1300,6 +1307,53 @@ __device__ __forceinline__ float wall_cast(const float4 wa, const float4 wb, V2 
   }
 #endif
   return (ok && index >= 0 && lower < bi) ? lower : bi;
+}
+
+// Opponent-aware sensors (nascar_set_car_visibility): b2PolygonShape::RayCast of the ray p1 -> p2 against the box of every
+// other car of car n's env, from the pass's pose records (pass A: pose[n], pass B: pose[N + n]; every writer of a pass
+// writes whole envs, so the other cars' records are valid whatever their mode words say).  Car j's box: centre the
+// record's (x, y) (the body origin), rotation b2Rot::Set of the record's float32 angle (the body's xf.q), half extents
+// CAR_HX, CAR_HY; the cast is wall_cast's, so face order, lower = 0 / upper = 1 and the f32 operations are the walls'.
+// A ray that starts inside a box gets no hit from it (index < 0).  Returns min(bi, hit fractions).
+// Two phases.  First wall_cast's first cull with the car's bounding radius (> sqrt(CAR_HX^2 + CAR_HY^2) = 2.80323, the
+// margin far above the f32 noise of the cast at <= 500 m) over every record, CAR_RAY_CHUNK records requested together
+// (independent loads: one memory latency per chunk -- one dependent load per car measured 5 us slower on the 8192 x 10
+// sensor launch, 8 per chunk no faster); run after the ray's wall walk, bi is small and most cars end there.  Then the survivors (a bit mask,
+// C <= 64): the record again, its sincosf and the cast.  The first phase culls with the wall hit, wall_cast repeats the
+// cull with the running best: both conservative, the result is the unculled minimum.  The 16 lanes of a car read the
+// same records (broadcast loads).
+#define CAR_RAY_R 2.81f
+#ifndef CAR_RAY_CHUNK
+#define CAR_RAY_CHUNK 4
+#endif
+__device__ __forceinline__ float car_casts(const Params& P, int n, int pass, V2 p1, float p2x, float p2y, float dx, float dy,
+                                           float bi) {
+  const int C = P.C;
+  const int first = (int)((unsigned)n / (unsigned)C) * C, self = n - first;
+  const float4* __restrict__ rec = P.pose + (pass == 0 ? (size_t)0 : (size_t)P.N) + first;
+  unsigned long long cand = 0ull;
+#pragma unroll 1
+  for (int j0 = 0; j0 < C; j0 += CAR_RAY_CHUNK) {
+    float2 o[CAR_RAY_CHUNK];
+#pragma unroll
+    for (int u = 0; u < CAR_RAY_CHUNK; ++u) o[u] = *(const float2*)(rec + min(j0 + u, C - 1));   // (x, y) of the record
+#pragma unroll
+    for (int u = 0; u < CAR_RAY_CHUNK; ++u) {
+      const int j = j0 + u;
+      const float rx = o[u].x - p1.x, ry = o[u].y - p1.y;
+      const float tc = rx * dx + ry * dy, perp = fabsf(rx * dy - ry * dx);
+      const bool out = perp > CAR_RAY_R || tc < -CAR_RAY_R || (tc - CAR_RAY_R) > 250.0f * bi;
+      if (j < C && j != self && !out) cand |= 1ull << (j & 63);
+    }
+  }
+  while (cand) {
+    const int j = __builtin_ctzll(cand);
+    cand &= cand - 1ull;
+    const float4 o = rec[j];
+    const Rot q = rot_set(o.z);
+    bi = wall_cast(make_float4(o.x, o.y, CAR_RAY_R, CAR_HX), make_float4(q.s, q.c, CAR_HY, 0.0f), p1, p2x, p2y, dx, dy, bi);
+  }
+  return bi;
 }
 
 // One ray without a beam list (car outside the cells build_beams covers): the sensor grid's wall groups
@@ -1512,7 +1566,8 @@ __device__ __forceinline__ int beam_slot0(double ang) {   // list slot of ray 0'
 // directly (64 contiguous bytes per car).
 // COOP: the wave-cooperative list continuations when every lane of the wave is here (16 lanes per car); false: every
 // ray walks its own list (callers whose lanes are not lockstep rays of whole cars, e.g. rt_switch_kernel)
-template <int LPC = RAY_LPC, bool GW = false, bool COOP = true>
+// VIS: the rays also see the env's other cars (car_casts after the ray's wall walks; false: today's code, no trace of it)
+template <int LPC = RAY_LPC, bool GW = false, bool COOP = true, bool VIS = false>
 __device__ __forceinline__ void ray_lane(const Params& P, const TrackDev& T, const float4* __restrict__ sw, int n, int r,
                                          float* obs, float* terminal_obs, int passes) {
   static_assert(LPC == 4 || LPC == 16, "lanes per car");
@@ -1602,6 +1657,7 @@ __device__ __forceinline__ void ray_lane(const Params& P, const TrackDev& T, con
         bi = ray_fallback(T, p1, p2.x, p2.y, dx, dy, ps.z, i);
       }
       if (LPC == 16 && coop) bi = ray_walk_coop<GW>(G, sw, kc, bi, p1, p2, dx, dy);   // (wave-uniform branch)
+      if constexpr (VIS) bi = car_casts(P, n, pass, p1, p2.x, p2.y, dx, dy, bi);
       PCOUNT(8, 1);
       if constexpr (RPL == 4) put4(v, q, sensor_value(bi));
       else v[q] = sensor_value(bi);
@@ -1714,7 +1770,7 @@ __device__ __forceinline__ void ray_block_batched(const Params& P, const TrackDe
 }
 // LPC lanes per car, BLOCK / LPC cars per workgroup; `sub` sensor workgroups per step-kernel workgroup (enough for
 // its epb * C cars)
-template <int LPC, int RB = BLOCK, bool GW = false>
+template <int LPC, int RB = BLOCK, bool GW = false, bool VIS = false>
 __global__ void __launch_bounds__(RB) __attribute__((amdgpu_waves_per_eu(RSENSOR_WPE)))
 ray_sensor_kernel(Params P, float* obs, float* terminal_obs, int passes, int SUB) {
   constexpr int CPW = RB / LPC;
@@ -1731,7 +1787,7 @@ ray_sensor_kernel(Params P, float* obs, float* terminal_obs, int passes, int SUB
   if constexpr (GW) {   // walls read from the track's global image: no staging, no LDS, no barrier
     PROFR(1);
     if (env < 0) return;
-    ray_lane<LPC, true>(P, T, T.swall, env * C + car, r, obs, terminal_obs, passes);
+    ray_lane<LPC, true, true, VIS>(P, T, T.swall, env * C + car, r, obs, terminal_obs, passes);
     PROFR(7); PROFR_RT(15);
     return;
   }
@@ -1743,7 +1799,7 @@ ray_sensor_kernel(Params P, float* obs, float* terminal_obs, int passes, int SUB
   }
   PROFR(1);
   if (env < 0) return;
-  ray_lane<LPC>(P, T, (const float4*)smem, env * C + car, r, obs, terminal_obs, passes);
+  ray_lane<LPC, false, true, VIS>(P, T, (const float4*)smem, env * C + car, r, obs, terminal_obs, passes);
   PROFR(7); PROFR_RT(15);
 }
 
@@ -3414,6 +3470,7 @@ struct NascarHandle {
   std::vector<int> pending_track;   // nascar_set_env_tracks, applied per env by its next nascar_reset
   bool pristine = true;             // no reset / step / rollout / set_state yet: track changes apply at once
   int car_contact = 0;              // nascar_set_car_contact (build-only extension)
+  int car_vis = 0;                  // nascar_set_car_visibility (build-only extension)
   int ray_lanes = 0;                // nascar_set_sensor_lanes: 0 automatic, 4 or 16 lanes per car
   // threads per ray_sensor_kernel workgroup at 16 lanes per car (nascar_set_sensor_block).  64 / 128: the walks read
   // the track's wall image from global memory (L2-resident); the workgroups need no LDS, so they start on any CU with
@@ -3671,6 +3728,8 @@ extern "C" int nascar_add_track(NascarHandle* h, const double* segments, int32_t
 static int sensor_lds_reserve(size_t need) {
   const void* kern[] = {(const void*)ray_sensor_kernel<4>, (const void*)ray_sensor_kernel<16>,
                         (const void*)ray_sensor_kernel<16, 512>, (const void*)ray_sensor_kernel<16, 1024>,
+                        (const void*)ray_sensor_kernel<4, BLOCK, false, true>, (const void*)ray_sensor_kernel<16, BLOCK, false, true>,
+                        (const void*)ray_sensor_kernel<16, 512, false, true>, (const void*)ray_sensor_kernel<16, 1024, false, true>,
                         (const void*)rollout_kernel};
   for (const void* k : kern) {
     hipFuncAttributes a;
@@ -4145,8 +4204,10 @@ static int ray_lpc(const NascarHandle* h) {
   return h->N <= RAY_LPC16_MAX_CARS ? 16 : 4;
 }
 // nb step-kernel workgroups from P.blk0 (each is `sub` sensor workgroups)
-static void launch_sensors_impl(NascarHandle* h, const Params& P, int nb, float* obs, float* terminal_obs, int passes,
-                                void* stream, int impl) {
+// VIS: the opponent-aware instantiations (nascar_set_car_visibility); false: the kernels as they are without the extension
+template <bool VIS>
+static void launch_sensors_vis(NascarHandle* h, const Params& P, int nb, float* obs, float* terminal_obs, int passes,
+                               void* stream, int impl) {
   if (impl == 1) {
     const size_t rlds = h->max_sensor_lds;   // >= 2 float4 per wall
     const int cars = h->epb * h->C;          // cars per step-kernel workgroup
@@ -4154,10 +4215,10 @@ static void launch_sensors_impl(NascarHandle* h, const Params& P, int nb, float*
       if (h->sensor_block < BLOCK) {   // 64 / 128 threads: the walls from the global image, no LDS
         const int rb = h->sensor_block, sub = (cars + rb / 16 - 1) / (rb / 16);
         if (rb == 64)
-          hipLaunchKernelGGL((ray_sensor_kernel<16, 64, true>), dim3(nb * sub), dim3(rb), 0, (hipStream_t)stream, P, obs,
+          hipLaunchKernelGGL((ray_sensor_kernel<16, 64, true, VIS>), dim3(nb * sub), dim3(rb), 0, (hipStream_t)stream, P, obs,
                              terminal_obs, passes, sub);
         else
-          hipLaunchKernelGGL((ray_sensor_kernel<16, 128, true>), dim3(nb * sub), dim3(rb), 0, (hipStream_t)stream, P, obs,
+          hipLaunchKernelGGL((ray_sensor_kernel<16, 128, true, VIS>), dim3(nb * sub), dim3(rb), 0, (hipStream_t)stream, P, obs,
                              terminal_obs, passes, sub);
         return;
       }
@@ -4166,25 +4227,37 @@ static void launch_sensors_impl(NascarHandle* h, const Params& P, int nb, float*
       while (rb > BLOCK && rb / 2 >= cars * 16) rb /= 2;   // no wider than a step workgroup's cars need (small batches)
       const int sub = (cars + rb / 16 - 1) / (rb / 16);
       if (rb == 1024)
-        hipLaunchKernelGGL((ray_sensor_kernel<16, 1024>), dim3(nb * sub), dim3(rb), rlds, (hipStream_t)stream, P, obs,
+        hipLaunchKernelGGL((ray_sensor_kernel<16, 1024, false, VIS>), dim3(nb * sub), dim3(rb), rlds, (hipStream_t)stream, P, obs,
                            terminal_obs, passes, sub);
       else if (rb == 512)
-        hipLaunchKernelGGL((ray_sensor_kernel<16, 512>), dim3(nb * sub), dim3(rb), rlds, (hipStream_t)stream, P, obs,
+        hipLaunchKernelGGL((ray_sensor_kernel<16, 512, false, VIS>), dim3(nb * sub), dim3(rb), rlds, (hipStream_t)stream, P, obs,
                            terminal_obs, passes, sub);
       else
-        hipLaunchKernelGGL((ray_sensor_kernel<16, BLOCK>), dim3(nb * sub), dim3(BLOCK), rlds, (hipStream_t)stream, P, obs,
+        hipLaunchKernelGGL((ray_sensor_kernel<16, BLOCK, false, VIS>), dim3(nb * sub), dim3(BLOCK), rlds, (hipStream_t)stream, P, obs,
                            terminal_obs, passes, sub);
     } else {
       const int sub = (cars + BLOCK / RAY_LPC - 1) / (BLOCK / RAY_LPC);
-      hipLaunchKernelGGL(ray_sensor_kernel<RAY_LPC>, dim3(nb * sub), dim3(BLOCK), rlds, (hipStream_t)stream, P, obs,
+      hipLaunchKernelGGL((ray_sensor_kernel<RAY_LPC, BLOCK, false, VIS>), dim3(nb * sub), dim3(BLOCK), rlds, (hipStream_t)stream, P, obs,
                          terminal_obs, passes, sub);
     }
     return;
   }
   const size_t lds = h->max_sensor_groups_lds;
   const int sub = (SBLOCK + BLOCK / SENSOR_LPC - 1) / (BLOCK / SENSOR_LPC);
-  hipLaunchKernelGGL(sensor_kernel<SENSOR_LPC>, dim3(nb * sub), dim3(BLOCK), lds, (hipStream_t)stream,
+  hipLaunchKernelGGL((sensor_kernel<SENSOR_LPC, VIS>), dim3(nb * sub), dim3(BLOCK), lds, (hipStream_t)stream,
                      P, obs, terminal_obs, passes);
+}
+static void launch_sensors_impl(NascarHandle* h, const Params& P, int nb, float* obs, float* terminal_obs, int passes,
+                                void* stream, int impl) {
+  if (h->car_vis) launch_sensors_vis<true>(h, P, nb, obs, terminal_obs, passes, stream, impl);
+  else launch_sensors_vis<false>(h, P, nb, obs, terminal_obs, passes, stream, impl);
+}
+// Car visibility with random-track mode is refused, not ignored: rt_switch_kernel's pass B casts walls only
+static int vis_refused(const NascarHandle* h) {
+  if (h->car_vis && h->rt_on)
+    return fail("car visibility (nascar_set_car_visibility) with random-track mode (nascar_set_random_tracks) is not "
+                "supported: switch one of them off");
+  return 0;
 }
 static void launch_sensors(NascarHandle* h, const Params& P, float* obs, float* terminal_obs, int passes, void* stream) {
   launch_sensors_impl(h, P, h->nblocks, obs, terminal_obs, passes, stream, sensor_impl());
@@ -4213,6 +4286,7 @@ static int rt_after_step(NascarHandle* h, const Params& P, const uint8_t* env_fl
 
 extern "C" int nascar_reset(NascarHandle* h, const uint8_t* env_mask, float* obs, void* stream) {
   if (!h || !obs) return fail("null argument");
+  if (vis_refused(h)) return -1;
   h->pristine = false;
   if (!h->rt_on && apply_pending_tracks(h, env_mask, stream)) return -1;
   if (prepare(h, (hipStream_t)stream)) return -1;
@@ -4315,6 +4389,7 @@ extern "C" int nascar_set_step_events(NascarHandle* h, void* const* events, int3
 static int step_impl(NascarHandle* h, const void* actions, int32_t discrete, int policy, uint64_t seed, int64_t step,
                      float* obs, float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset,
                      float* terminal_obs, void* stream) {
+  if (vis_refused(h)) return -1;
   h->pristine = false;
   if (prepare(h, (hipStream_t)stream)) return -1;
   Params P = make_params(h);
@@ -4547,10 +4622,15 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
   if ((traj & NASCAR_TRAJ_OBS) && !(traj & NASCAR_TRAJ_RECORDS)) return fail("an obs trajectory needs the per-step records (traj bit 0)");
   if ((traj & NASCAR_TRAJ_OBS) && h->ro_streams == 0) return fail("obs trajectories need the sharded rollout (rollout streams >= 1)");
   if (steps < 0) return fail("steps must be >= 0");
+  if (vis_refused(h)) return -1;
+  if (h->car_vis && h->ro_streams == 0)
+    return fail("car visibility (nascar_set_car_visibility) with the fused single-launch rollout (rollout streams 0) is not "
+                "supported: use the sharded rollout (rollout streams >= 1)");
   if (steps == 0) return 0;
   h->pristine = false;
   if (prepare(h, (hipStream_t)stream)) return -1;
-  if (h->ro_pipe > 0 && policy != 2 && policy != 4 && !h->rt_on && !h->car_contact && !(traj & NASCAR_TRAJ_OBS))
+  // the pipelined schedule's sensor kernel casts walls only: car contact, car visibility and the others fall back to the streams
+  if (h->ro_pipe > 0 && policy != 2 && policy != 4 && !h->rt_on && !h->car_contact && !h->car_vis && !(traj & NASCAR_TRAJ_OBS))
     return rollout_pipe(h, policy, seed, step0, steps, obs, reward, car_flags, env_flags, auto_reset, traj,
                         (hipStream_t)stream);
   if (h->ro_streams > 0)
@@ -4676,6 +4756,13 @@ extern "C" int nascar_set_car_contact(NascarHandle* h, int32_t enable) {
   h->car_contact = enable ? 1 : 0;
   return 0;
 }
+
+extern "C" int nascar_set_car_visibility(NascarHandle* h, int32_t enable) {
+  if (!h) return fail("null argument");
+  h->car_vis = enable ? 1 : 0;
+  return 0;
+}
+extern "C" int nascar_get_car_visibility(NascarHandle* h) { return h ? h->car_vis : -1; }
 
 extern "C" int nascar_set_perf_history(NascarHandle* h, int32_t enable, void* stream) {
   if (!h) return fail("null argument");

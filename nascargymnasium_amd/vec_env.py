@@ -326,6 +326,12 @@ class VecCarEnv:
             self._set_seeds(np.array([seed_value], np.uint64), [e])
         return [seed_value]
 
+    def _env_set_car_visibility(self, e, enable=True):
+        """BatchedCarEnv.set_car_visibility (build-only extension: the sensors see the env's other cars).  The switch
+        belongs to the engine, so it holds for every sub-env whichever indices are named; returns the setting."""
+        self.engine.set_car_visibility(enable)
+        return self.engine.car_visibility
+
     def _env_render(self, e, *a, **k):
         return None
 
