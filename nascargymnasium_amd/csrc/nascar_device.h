@@ -16,12 +16,8 @@
 
 #pragma clang fp contract(off)
 
-#ifndef BLOCK
 #define BLOCK 256   // threads per workgroup of the sensor kernel
-#endif
-#ifndef SBLOCK
 #define SBLOCK 128  // threads per workgroup of the one-lane-per-car kernels (whole envs)
-#endif
 
 #ifdef NASCAR_PROFILE
 // profile build only: per-wave s_memtime stamps at phase boundaries of step_kernel
@@ -295,9 +291,7 @@ struct WallGrid {
   const uint16_t* idx;
   const float4* box;       // bp only: fat AABB (lo.x, lo.y, hi.x, hi.y) of wall idx[k], padded by BP_BATCH entries
 };
-#ifndef BP_BATCH
-#define BP_BATCH 4   // broadphase candidates whose boxes are loaded together (0: one wall record at a time)
-#endif
+#define BP_BATCH 4   // broadphase candidates whose boxes are loaded together
 struct WallSet {
   const LWall* W; int nw;
   WallGrid bp, sn;
@@ -439,9 +433,6 @@ __device__ inline void add_pair(Car& c, const WallSet& S, int j) {
 }
 // b2BroadPhase::UpdatePairs + b2ContactManager::AddPair (ascending wall proxy id, prepend)
 __device__ inline void find_new_contacts(Car& c, const WallSet& S) {
-#ifdef NASCAR_KO_FIND
-  c.moved = 0; return;
-#endif
   if (!c.moved) return;
   c.moved = 0;
   const LWall* W = S.W;
@@ -453,7 +444,6 @@ __device__ inline void find_new_contacts(Car& c, const WallSet& S) {
     if (hx <= S.bp.reach - 0.05f && hy <= S.bp.reach - 0.05f && grid_list(S.bp, cx, cy, beg, end)) list = S.bp.idx;
     else { beg = 0; end = S.nw; CCOUNT(c, 8, 1); }
   }
-#if BP_BATCH > 0
   if (list && S.bp.box) {
     // the cell's candidate boxes stored in list order: BP_BATCH independent loads per round instead of a
     // dependent (index -> wall record) pair per candidate; same candidates, same ascending order
@@ -471,7 +461,6 @@ __device__ inline void find_new_contacts(Car& c, const WallSet& S) {
     }
     return;
   }
-#endif
   for (int k = beg; k < end; ++k) {
     const int j = list ? (int)ldg(list + k) : k;
     if (!overlap(c.fat, fat_box(ldg(S.fat + j)))) continue;
@@ -721,8 +710,6 @@ struct ToiWaveLDS { float4 sw0[64], sw1[64]; int2 job[TOI_JOBCAP]; float res[TOI
 #define MANI_JOBCAP 32    // event manifolds per wave and scan computed cooperatively (the rest by their owners)
 #endif
 struct ManiWaveLDS { float4 xf[64]; int2 job[MANI_JOBCAP]; ManiRes res[MANI_JOBCAP]; };
-#define BP_JOBCAP 128     // broadphase candidate tests per wave and round
-struct BpWaveLDS { float4 fat[64]; int2 job[BP_JOBCAP]; unsigned int hit[64][2]; };
 // b2ContactSolver constraint of one (car, wall) contact (register-resident for small islands; see solve_island)
 struct VCP { V2 rA, rB; float ni, ti, nm, tm, vb; };
 struct VC {
@@ -731,9 +718,11 @@ struct VC {
   V2 ln, lp, lps[2]; int pcount, type, ci;
   Rot qB; uint32_t aB0;   // the static wall's b2Rot (its body transform) and the angle bits it was set from
 };
-// the general (more than ISLAND_MID contacts) island's constraints, one lane at a time (solve_island_general)
+// the general (more than 2 contacts) island's constraints, one lane at a time (solve_island_general)
 struct IslandWaveLDS { VC vc[MAX_ISLAND]; };
-union WaveLDS { ToiWaveLDS toi; ManiWaveLDS mani; BpWaveLDS bp; IslandWaveLDS island; };
+// (floor: the area is 2560 bytes at least, so test builds with small job caps keep the LDS layout they always had;
+// the product's ToiWaveLDS is larger)
+union WaveLDS { ToiWaveLDS toi; ManiWaveLDS mani; IslandWaveLDS island; float4 floor[160]; };
 static_assert(sizeof(IslandWaveLDS) <= sizeof(ToiWaveLDS), "the island area must not grow the wave's LDS work area");
 __shared__ WaveLDS g_wave_lds[SBLOCK / 64];   // model_kernel / rollout_kernel (the Box2D step)
 __device__ __forceinline__ void wave_lds_sync() {   // a wave's LDS writes visible to its later LDS reads
@@ -775,53 +764,18 @@ __device__ __forceinline__ Rot rot_static(float a, uint32_t a0bits, Rot q0) {
 }
 struct BodyState { V2 c; float a; V2 v; float w; };
 // unroll count of the per-contact loops below: full for islands of <= 2 contacts (register-resident), else a loop
-#define UNROLL_SMALL NUNR<NMAX>::v
-// A contact constraint of the general (scratch-memory) island is copied into registers for its loop body and
-// written back at its end: one burst of independent scratch loads per contact and pass instead of a dependent
-// scratch round trip per field use (register-resident small islands: the same code, the copies fold away)
-#ifndef ISLAND_COPY
-#define ISLAND_COPY 0   // measured: 81 VGPRs spilled kernel-wide, 212 vs 160 us/step (off)
-#endif
-#if ISLAND_COPY
-#define VC_BEGIN(i) VC v = vc[i]
-#define VC_END(i) vc[i] = v
-#else
-#define VC_BEGIN(i) VC& v = vc[i]
-#define VC_END(i) (void)0
-#endif
-#ifndef ISLAND_MID
-// islands of 3 .. ISLAND_MID contacts also solved register-resident (0: off).  2 (round 4): 3-contact islands go to the
-// LDS general solver -- the fully unrolled 3-contact register solver took ~50 k cycles against ~19 k for 1-2 contacts,
-// and dropping it leaves model_kernel / model_logic_kernel spill-free (233 / 244 VGPRs instead of 256 with 15 / 22
-// spilled): driver's command 148.1 / 149.7 -> 143.3 / 144.8 us per step.  (3 measured faster in round 2, before the
-// general island moved out of scratch memory; 4 slower.)
-#define ISLAND_MID 2
-#endif
-// ISLAND_TWO = 2: islands of 1-2 contacts have their own register-resident solver; 0: they share the
-// ISLAND_MID one (one solver instance less per island kind: a wave whose lanes hold islands of 1 and of 3 contacts
-// then runs one solver, not two in turn)
-#ifndef ISLAND_TWO
-#define ISLAND_TWO 2
-#endif
-template <int NMAX> struct NUNR { static constexpr int v = NMAX <= 2 || NMAX == ISLAND_MID ? NMAX : 1; };
+#define UNROLL_SMALL NMAX <= 2 ? NMAX : 1
 // The solvers' iteration loops (6 velocity, 4 / 20 position iterations) index nothing per iteration, so rolled
 // loops keep the constraints in the same registers; unrolled, each island size's solver was copied six times over
 // (cs_solve_velocity alone was 34 KB of model_kernel's 295 KB of code, a kernel far beyond the instruction cache).
-#ifndef SOLVER_ITER_UNROLL
-#define SOLVER_ITER_UNROLL 0
-#endif
-#if SOLVER_ITER_UNROLL
-#define SOLVER_ITER_LOOP
-#else
 #define SOLVER_ITER_LOOP _Pragma("unroll 1")
-#endif
 
 template <int NMAX> __device__ __forceinline__ void cs_init(VC* vc, int n, const Car& c, const int* cidx, const LWall* W, bool warm, float dtRatio) {
 #pragma unroll UNROLL_SMALL   // registers for small islands; the general bound stays a loop
   for (int i = 0; i < NMAX; ++i) {
     if (i >= n) break;
     const DContact& ct = c.ct[cidx[i]];
-    VC_BEGIN(i);
+    VC& v = vc[i];
     v.ci = cidx[i];
     v.pointCount = ct.pointCount;
     const LWall wl = ldg(W + ct.wall);
@@ -839,7 +793,6 @@ template <int NMAX> __device__ __forceinline__ void cs_init(VC* vc, int n, const
       if (warm) { v.p[j].ni = dtRatio * ct.pt[j].ni; v.p[j].ti = dtRatio * ct.pt[j].ti; }
       v.lps[j] = V(ct.pt[j].lx, ct.pt[j].ly);
     }
-    VC_END(i);
   }
 }
 
@@ -850,7 +803,7 @@ template <int NMAX> __device__ __forceinline__ void cs_init_velocity(VC* vc, int
 #pragma unroll UNROLL_SMALL   // registers for small islands; the general bound stays a loop
   for (int i = 0; i < NMAX; ++i) {
     if (i >= n) break;
-    VC_BEGIN(i);
+    VC& v = vc[i];
     const DContact& m = c.ct[v.ci];
     V2 cA = A.c; float aA = A.a; V2 vA = A.v; float wA = A.w;
     V2 cB = v.cB; float aB = v.aB; V2 vB = v.vB; float wB = v.wB;
@@ -893,7 +846,6 @@ template <int NMAX> __device__ __forceinline__ void cs_init_velocity(VC* vc, int
         v.pointCount = 1;
       }
     }
-    VC_END(i);
   }
 }
 
@@ -902,7 +854,7 @@ template <int NMAX> __device__ __forceinline__ void cs_warm_start(VC* vc, int n,
 #pragma unroll UNROLL_SMALL   // registers for small islands; the general bound stays a loop
   for (int i = 0; i < NMAX; ++i) {
     if (i >= n) break;
-    VC_BEGIN(i);
+    VC& v = vc[i];
     V2 vA = A.v; float wA = A.w; V2 vB = v.vB; float wB = v.wB;
     V2 normal = v.normal, tangent = vcross_vs(normal, 1.0f);
     for (int j = 0; j < 2; ++j) {
@@ -915,7 +867,6 @@ template <int NMAX> __device__ __forceinline__ void cs_warm_start(VC* vc, int n,
       vB = vadd(vB, vmul(mB, P));
     }
     A.v = vA; A.w = wA; v.vB = vB; v.wB = wB;
-    VC_END(i);
   }
 }
 
@@ -928,7 +879,7 @@ template <int NMAX> __device__ __forceinline__ void cs_solve_velocity(VC* vc, in
 #pragma unroll UNROLL_SMALL   // registers for small islands; the general bound stays a loop
   for (int i = 0; i < NMAX; ++i) {
     if (i >= n) break;
-    VC_BEGIN(i);
+    VC& v = vc[i];
     V2 vA = A.v; float wA = A.w; V2 vB = v.vB; float wB = v.wB;
     V2 normal = v.normal, tangent = vcross_vs(normal, 1.0f);
     for (int j = 0; j < 2; ++j) {
@@ -993,7 +944,6 @@ template <int NMAX> __device__ __forceinline__ void cs_solve_velocity(VC* vc, in
       }
     }
     A.v = vA; A.w = wA; v.vB = vB; v.wB = wB;
-    VC_END(i);
   }
 }
 
@@ -1020,7 +970,7 @@ template <int NMAX> __device__ __forceinline__ int cs_solve_position(VC* vc, int
 #pragma unroll UNROLL_SMALL   // registers for small islands; the general bound stays a loop
   for (int i = 0; i < NMAX; ++i) {
     if (i >= n) break;
-    VC_BEGIN(i);
+    VC& v = vc[i];
     V2 cA = A.c; float aA = A.a; V2 cB = v.cB; float aB = v.aB;
     for (int j = 0; j < 2; ++j) {
       if (j >= v.pcount) break;
@@ -1049,7 +999,6 @@ template <int NMAX> __device__ __forceinline__ int cs_solve_position(VC* vc, int
       cB = vadd(cB, vmul(mB, P)); aB += iB * vcross(rB, P);
     }
     A.c = cA; A.a = aA; v.cB = cB; v.aB = aB;
-    VC_END(i);
   }
   return toi ? (minSep >= -1.5f * LINEAR_SLOP) : (minSep >= -3.0f * LINEAR_SLOP);
 }
@@ -1122,14 +1071,11 @@ __device__ __forceinline__ int solve_island(Car& c, const LWall* W, const int* c
   VC vc[NMAX];   // small islands: fully unrolled, register-resident
   return solve_island_buf<NMAX>(c, W, cidx, n, dt, dtRatio, friction, vc);
 }
-// The general island (more than ISLAND_MID touching contacts) indexes its constraints dynamically; as a private
+// The general island (more than 2 touching contacts) indexes its constraints dynamically; as a private
 // array they would live in scratch memory (1.6 KB per lane, a vector-memory round trip per field use).  Instead
 // the wave's LDS work area (free during b2World::Solve and an event's island solve) holds them, one lane at a time
 // -- the lowest lane of the wave still waiting goes next.  Divergent lanes of a wave run one after another anyway,
 // so serialising them costs nothing over the private-array form; every access is an LDS round trip.
-#ifndef ISLAND_LDS
-#define ISLAND_LDS 1
-#endif
 template <typename F>
 __device__ __forceinline__ void wave_lds_one_at_a_time(F&& body) {
   unsigned long long pending = __ballot(1);   // the lanes of this wave executing this call
@@ -1143,79 +1089,9 @@ __device__ __forceinline__ void wave_lds_one_at_a_time(F&& body) {
 }
 __device__ __forceinline__ int solve_island_general(Car& c, const LWall* W, const int* cidx, int n, float dt,
                                                    float dtRatio, float friction) {
-#if ISLAND_LDS
   int r = 0;
   wave_lds_one_at_a_time([&](VC* vc) { r = solve_island_buf<MAX_ISLAND>(c, W, cidx, n, dt, dtRatio, friction, vc); });
   return r;
-#else
-  return solve_island<MAX_ISLAND>(c, W, cidx, n, dt, dtRatio, friction);
-#endif
-}
-
-// b2BroadPhase::UpdatePairs of b2World::Solve for every lane of the wave at once (round 3).  A moved car's grid
-// cell lists its candidate walls in ascending proxy id; here every present lane tests any (car, candidate) pair of
-// the wave -- the candidate's fat AABB against the owner's, read from LDS -- and sets the pair's bit in the owner's
-// hit mask, then each owner runs AddPair for its hits in ascending candidate order: the same pairs in the same
-// order as find_new_contacts' own loop, with one round of independent loads per wave instead of a dependent chain
-// per car.  Lists longer than 64 candidates, queries outside the grid or wider than its reach take the car's own scan.
-#ifndef BP_COOP
-#define BP_COOP 0   // measured neutral (160.7 vs 159.2 us/step, 3 A/B rounds): the broadphase chain is not its candidate loads
-#endif
-#ifndef MODEL_PRIO
-#define MODEL_PRIO 0   // wave priority experiments (0: off)
-#endif
-__device__ inline void find_new_contacts_wave(Car& c, const WallSet& S, bool want) {
-  bool mine = false; int beg = 0, end = 0;
-  if (want && c.moved) {
-    const float hx = 0.5f * (c.fat.hi.x - c.fat.lo.x), hy = 0.5f * (c.fat.hi.y - c.fat.lo.y);
-    const float cx = 0.5f * (c.fat.hi.x + c.fat.lo.x), cy = 0.5f * (c.fat.hi.y + c.fat.lo.y);
-    if (S.bp.box && hx <= S.bp.reach - 0.05f && hy <= S.bp.reach - 0.05f && grid_list(S.bp, cx, cy, beg, end) &&
-        end - beg <= 64) {
-      mine = true;
-      c.moved = 0;
-    } else {
-      find_new_contacts(c, S);
-    }
-  }
-  if (!__ballot(mine)) return;   // wave-uniform
-  BpWaveLDS& B = g_wave_lds[threadIdx.x >> 6].bp;
-  const int lane = (int)__lane_id();
-  const unsigned long long present = __ballot(1);
-  const int prank = rank_in(present), npresent = popc64(present);
-  const int m = mine ? end - beg : 0;
-  int off = 0, total = 0;
-#pragma unroll
-  for (int bit = 0; bit < 7; ++bit) {
-    const unsigned long long b = __ballot((m >> bit) & 1);
-    off += rank_in(b) << bit;
-    total += popc64(b) << bit;
-  }
-  if (mine) { B.fat[lane] = make_float4(c.fat.lo.x, c.fat.lo.y, c.fat.hi.x, c.fat.hi.y); B.hit[lane][0] = 0u; B.hit[lane][1] = 0u; }
-  for (int r0 = 0; r0 < total; r0 += BP_JOBCAP) {   // wave-uniform
-    if (mine) {
-      const int k1 = min(off + m, r0 + BP_JOBCAP);
-      for (int k = max(off, r0); k < k1; ++k) B.job[k - r0] = make_int2(lane | ((k - off) << 8), beg + (k - off));
-    }
-    wave_lds_sync();
-    const int cnt = min(BP_JOBCAP, total - r0);
-    for (int j = prank; j < cnt; j += npresent) {
-      const int2 jb = B.job[j];
-      const int owner = jb.x & 0xFF, q = jb.x >> 8;
-      const float4 f = B.fat[owner], b = ldg(S.bp.box + jb.y);
-      Aabb fa; fa.lo = V(f.x, f.y); fa.hi = V(f.z, f.w);
-      Aabb bb; bb.lo = V(b.x, b.y); bb.hi = V(b.z, b.w);
-      if (overlap(fa, bb)) atomicOr(&B.hit[owner][q >> 5], 1u << (q & 31));
-    }
-    wave_lds_sync();
-  }
-  if (mine) {
-    unsigned long long h = (unsigned long long)B.hit[lane][0] | ((unsigned long long)B.hit[lane][1] << 32);
-    while (h) {
-      const int q = __ffsll((long long)h) - 1; h &= h - 1;
-      add_pair(c, S, (int)ldg(S.bp.idx + beg + q));
-    }
-  }
-  wave_lds_sync();   // hit masks read before the union's next use
 }
 
 // b2World::Solve (single dynamic body island)
@@ -1232,14 +1108,10 @@ __device__ inline void solve(Car& c, const WallSet& S, float dt, float dtRatio, 
   const float h = dt;
   CCOUNT(c, 26, n);   // profile builds: the island's touching contacts and its solve cycles (slot 25)
   CTIME_BEGIN();
-#if ISLAND_MID
-  const int positionSolved = n <= ISLAND_TWO ? solve_island<2>(c, W, cidx, n, dt, dtRatio, friction)
-                           : n <= ISLAND_MID ? solve_island<ISLAND_MID>(c, W, cidx, n, dt, dtRatio, friction)
-                                             : solve_island_general(c, W, cidx, n, dt, dtRatio, friction);
-#else
+  // islands of 3+ contacts go to the LDS general solver: a register-resident 3-contact solver took ~50 k cycles
+  // against ~19 k for 1-2 contacts and made model_kernel spill (148.1 -> 143.3 us per step without it)
   const int positionSolved = n <= 2 ? solve_island<2>(c, W, cidx, n, dt, dtRatio, friction)
-                                    : solve_island<MAX_ISLAND>(c, W, cidx, n, dt, dtRatio, friction);
-#endif
+                                  : solve_island_general(c, W, cidx, n, dt, dtRatio, friction);
   CTIME_END(c, 25);
   {
     float minSleepTime = FLT_BIG;
@@ -1257,35 +1129,26 @@ __device__ inline void solve(Car& c, const WallSet& S, float dt, float dtRatio, 
   sync_fixtures(c);
   CTIME_END(c, 22);
   }
-#if !BP_COOP   // (else b2_step runs the wave's broadphase updates together: find_new_contacts_wave)
   {
   CTIME_BEGIN();
   if (c.moved) CCOUNT(c, 24, 1);
   find_new_contacts(c, S);
   CTIME_END(c, 21);
   }
-#endif
 }
 
 // ------------------------------------------------------------------ GJK / TOI
-// b2Distance (GJK) with the simplex vertices and the cache indices as named values (no dynamically indexed
-// arrays: those lived in scratch memory).  Same operations in the same order as b2Simplex::ReadCache /
-// Solve2 / Solve3 / GetSearchDirection / GetWitnessPoints / WriteCache.
-struct SV { V2 wA, wB, w; float a; int iA, iB; };
+// b2SimplexCache with the cache indices as named values (no dynamically indexed arrays: those lived in scratch memory)
 struct SCache { float metric; int count; int iA0, iA1, iA2, iB0, iB1, iB2;
 #ifdef NASCAR_PROFILE
   int iters = 0;   // profile builds: GJK iterations summed over the calls that used this cache
 #endif
 };
 
-#ifndef SUPPORT_BOX
-#define SUPPORT_BOX 1
-#endif
 // b2PolygonShape / b2DistanceProxy::GetSupport: the first vertex of maximal dot product with d.  For a box the four
 // dot products (+-hx) dx + (+-hy) dy share the two products a = hx dx, b = hy dy ((-hx) dx is -(hx dx) exactly in
 // IEEE arithmetic), so they are (-a) + (-b), a + (-b), a + b, (-a) + b -- the same values, 2 products instead of 8.
 __device__ __forceinline__ int support(const Poly* p, V2 d) {
-#if SUPPORT_BOX
   const float a = p->hx * d.x, b = p->hy * d.y;
   const float v1 = a + (-b), v2 = a + b, v3 = (-a) + b;
   int best = 0; float bestValue = (-a) + (-b);
@@ -1293,27 +1156,7 @@ __device__ __forceinline__ int support(const Poly* p, V2 d) {
   if (v2 > bestValue) { best = 2; bestValue = v2; }
   if (v3 > bestValue) { best = 3; }
   return best;
-#else
-  int best = 0; float bestValue = vdot(pv(p, 0), d);
-  for (int i = 1; i < 4; ++i) { float value = vdot(pv(p, i), d); if (value > bestValue) { best = i; bestValue = value; } }
-  return best;
-#endif
 }
-__device__ __forceinline__ float simplex_metric(int count, const SV& v0, const SV& v1, const SV& v2) {
-  if (count == 1) return 0.0f;
-  if (count == 2) return vlen(vsub(v0.w, v1.w));
-  if (count == 3) return vcross(vsub(v1.w, v0.w), vsub(v2.w, v0.w));
-  return 0.0f;
-}
-__device__ __forceinline__ void sv_set(SV& v, int ia, int ib, const Poly* pA, Xf tA, const Poly* pB, Xf tB) {
-  v.iA = ia; v.iB = ib;
-  v.wA = xmul(tA, pv(pA, ia)); v.wB = xmul(tB, pv(pB, ib));
-  v.w = vsub(v.wB, v.wA); v.a = 0.0f;
-}
-#ifndef GJK_V2
-#define GJK_V2 1
-#endif
-#if GJK_V2
 // b2Distance (b2GJK) for two boxes, restated for a short dependent chain: the simplex is held as its vertices' w
 // (= wB - wA), packed index pairs (iA | iB << 2) and barycentric weights only -- the support points wA / wB are
 // recomputed from their indices where b2Simplex::GetWitnessPoints needs them (b2Transform * vertex again: the same
@@ -1423,103 +1266,6 @@ __device__ inline float gjk_distance(SCache& cache, const Poly* pA, Xf tA, const
   cache.iA0 = i0 & 3; cache.iB0 = i0 >> 2; cache.iA1 = i1 & 3; cache.iB1 = i1 >> 2; cache.iA2 = i2 & 3; cache.iB2 = i2 >> 2;
   return vlen(vsub(wa, wb));
 }
-#else
-__device__ inline float gjk_distance(SCache& cache, const Poly* pA, Xf tA, const Poly* pB, Xf tB) {
-  SV v0, v1, v2;
-  v0.wA = v0.wB = v0.w = zero2(); v0.a = 0.0f; v0.iA = v0.iB = 0;
-  v2 = v1 = v0;
-  int count = cache.count;
-  if (count > 0) sv_set(v0, cache.iA0, cache.iB0, pA, tA, pB, tB);
-  if (count > 1) sv_set(v1, cache.iA1, cache.iB1, pA, tA, pB, tB);
-  if (count > 2) sv_set(v2, cache.iA2, cache.iB2, pA, tA, pB, tB);
-  if (count > 1) {
-    float metric1 = cache.metric, metric2 = simplex_metric(count, v0, v1, v2);
-    if (metric2 < 0.5f * metric1 || 2.0f * metric1 < metric2 || metric2 < FLT_EPS) count = 0;
-  }
-  if (count == 0) {
-    sv_set(v0, 0, 0, pA, tA, pB, tB);
-    v0.a = 1.0f;
-    count = 1;
-  }
-  int sA0 = 0, sA1 = 0, sA2 = 0, sB0 = 0, sB1 = 0, sB2 = 0, saveCount = 0, iter = 0;
-  while (iter < 20) {
-    saveCount = count;
-    sA0 = v0.iA; sB0 = v0.iB; sA1 = v1.iA; sB1 = v1.iB; sA2 = v2.iA; sB2 = v2.iB;
-    if (count == 2) {
-      V2 w1 = v0.w, w2 = v1.w, e12 = vsub(w2, w1);
-      float d12_2 = -vdot(w1, e12);
-      if (d12_2 <= 0.0f) { v0.a = 1.0f; count = 1; }
-      else {
-        float d12_1 = vdot(w2, e12);
-        if (d12_1 <= 0.0f) { v1.a = 1.0f; count = 1; v0 = v1; }
-        else { float inv = fdiv_cr(1.0f, d12_1 + d12_2); v0.a = d12_1 * inv; v1.a = d12_2 * inv; count = 2; }
-      }
-    } else if (count == 3) {
-      V2 w1 = v0.w, w2 = v1.w, w3 = v2.w;
-      V2 e12 = vsub(w2, w1);
-      float d12_1 = vdot(w2, e12), d12_2 = -vdot(w1, e12);
-      V2 e13 = vsub(w3, w1);
-      float d13_1 = vdot(w3, e13), d13_2 = -vdot(w1, e13);
-      V2 e23 = vsub(w3, w2);
-      float d23_1 = vdot(w3, e23), d23_2 = -vdot(w2, e23);
-      float n123 = vcross(e12, e13);
-      float d123_1 = n123 * vcross(w2, w3), d123_2 = n123 * vcross(w3, w1), d123_3 = n123 * vcross(w1, w2);
-      if (d12_2 <= 0.0f && d13_2 <= 0.0f) { v0.a = 1.0f; count = 1; }
-      else if (d12_1 > 0.0f && d12_2 > 0.0f && d123_3 <= 0.0f) {
-        float inv = fdiv_cr(1.0f, d12_1 + d12_2); v0.a = d12_1 * inv; v1.a = d12_2 * inv; count = 2;
-      } else if (d13_1 > 0.0f && d13_2 > 0.0f && d123_2 <= 0.0f) {
-        float inv = fdiv_cr(1.0f, d13_1 + d13_2); v0.a = d13_1 * inv; v2.a = d13_2 * inv; count = 2; v1 = v2;
-      } else if (d12_1 <= 0.0f && d23_2 <= 0.0f) { v1.a = 1.0f; count = 1; v0 = v1; }
-      else if (d13_1 <= 0.0f && d23_1 <= 0.0f) { v2.a = 1.0f; count = 1; v0 = v2; }
-      else if (d23_1 > 0.0f && d23_2 > 0.0f && d123_1 <= 0.0f) {
-        float inv = fdiv_cr(1.0f, d23_1 + d23_2); v1.a = d23_1 * inv; v2.a = d23_2 * inv; count = 2; v0 = v2;
-      } else {
-        float inv = fdiv_cr(1.0f, d123_1 + d123_2 + d123_3);
-        v0.a = d123_1 * inv; v1.a = d123_2 * inv; v2.a = d123_3 * inv; count = 3;
-      }
-    }
-    if (count == 3) break;
-    V2 d;
-    if (count == 1) d = vneg(v0.w);
-    else {
-      V2 e12 = vsub(v1.w, v0.w);
-      float sgn = vcross(e12, vneg(v0.w));
-      d = sgn > 0.0f ? vcross_sv(1.0f, e12) : vcross_vs(e12, 1.0f);
-    }
-    if (vdot(d, d) < FLT_EPS * FLT_EPS) break;
-    SV vx;
-    vx.iA = support(pA, rmulT(tA.q, vneg(d)));
-    vx.wA = xmul(tA, pv(pA, vx.iA));
-    vx.iB = support(pB, rmulT(tB.q, d));
-    vx.wB = xmul(tB, pv(pB, vx.iB));
-    vx.w = vsub(vx.wB, vx.wA);
-    vx.a = 0.0f;
-    ++iter;
-#ifdef NASCAR_PROFILE
-    ++cache.iters;
-#endif
-    bool dup = (vx.iA == sA0 && vx.iB == sB0) || (saveCount > 1 && vx.iA == sA1 && vx.iB == sB1) ||
-               (saveCount > 2 && vx.iA == sA2 && vx.iB == sB2);
-    if (dup) break;
-    if (count == 1) v1 = vx; else v2 = vx;
-    ++count;
-  }
-  V2 wa = zero2(), wb = zero2();
-  if (count == 1) { wa = v0.wA; wb = v0.wB; }
-  else if (count == 2) {
-    wa = vadd(vmul(v0.a, v0.wA), vmul(v1.a, v1.wA));
-    wb = vadd(vmul(v0.a, v0.wB), vmul(v1.a, v1.wB));
-  } else if (count == 3) {
-    wa = vadd(vadd(vmul(v0.a, v0.wA), vmul(v1.a, v1.wA)), vmul(v2.a, v2.wA));
-    wb = wa;
-  }
-  cache.metric = simplex_metric(count, v0, v1, v2);
-  cache.count = count;
-  cache.iA0 = v0.iA; cache.iB0 = v0.iB; cache.iA1 = v1.iA; cache.iB1 = v1.iB; cache.iA2 = v2.iA; cache.iB2 = v2.iB;
-  return vlen(vsub(wa, wb));
-}
-
-#endif
 
 struct Sweep { V2 c0, c; float a0, a, alpha0; };
 __device__ __forceinline__ Xf sweep_xf(const Sweep& s, float beta) {
@@ -1734,15 +1480,8 @@ __device__ __forceinline__ void island_solve_toi_n(Car& c, const LWall* W, const
   island_solve_toi_buf<NMAX>(c, W, cidx, n, subdt, friction, vc);
 }
 __device__ inline void island_solve_toi(Car& c, const LWall* W, const int* cidx, int n, float subdt, float friction) {
-  if (n <= ISLAND_TWO) island_solve_toi_n<2>(c, W, cidx, n, subdt, friction);
-#if ISLAND_MID
-  else if (n <= ISLAND_MID) island_solve_toi_n<ISLAND_MID>(c, W, cidx, n, subdt, friction);
-#endif
-#if ISLAND_LDS   // the general TOI island in the wave's LDS work area, one lane at a time (see solve_island_general)
+  if (n <= 2) island_solve_toi_n<2>(c, W, cidx, n, subdt, friction);
   else wave_lds_one_at_a_time([&](VC* vc) { island_solve_toi_buf<MAX_ISLAND>(c, W, cidx, n, subdt, friction, vc); });
-#else
-  else island_solve_toi_n<MAX_ISLAND>(c, W, cidx, n, subdt, friction);
-#endif
 }
 
 // Exact shortcut for b2TimeOfImpact on a (car, static wall) pair.  The root finder can only report
@@ -1782,9 +1521,6 @@ __device__ __forceinline__ float toi_gap_bound(V2 u, V2 d, V2 dc, V2 cx, V2 cy, 
 // few mrad per step) from being culled; its second-order replacement is ~1e-5 m.  The start pose's rotation is the
 // end pose's b2Rot rotated back by a - a0 (Taylor terms to |a - a0|^5, error < 1e-7 for |a - a0| <= 0.1; larger
 // rotations are not culled here).
-#ifndef TOI_CULL2
-#define TOI_CULL2 1
-#endif
 __device__ __forceinline__ float toi_gap2(V2 u, V2 d1, V2 d0, V2 cx1, V2 cy1, V2 cx0, V2 cy0, float wext) {
   const float s1 = vdot(u, d1), s0 = vdot(u, d0);
   const float g1 = fabsf(s1) - (CAR_HX * fabsf(vdot(u, cx1)) + CAR_HY * fabsf(vdot(u, cy1))) - wext;
@@ -1809,9 +1545,6 @@ __device__ __forceinline__ bool toi_far_rot2(const Car& c, const LWall& wl, V2 d
   return b - d2 * (R_CAR * 0.125f) > TOI_CULL_DIST;
 }
 __device__ __forceinline__ bool toi_far(const Car& c, const Poly* pa, const LWall& wl) {
-#ifdef NASCAR_NO_TOI_CULL   // A/B and verification builds only
-  return false;
-#endif
   (void)pa;
   const float R_CAR = 2.80389f;   // > sqrt(CAR_HX^2 + CAR_HY^2) = 2.80323
   const V2 cx = V(c.xf.q.c, c.xf.q.s), cy = V(-c.xf.q.s, c.xf.q.c);
@@ -1823,11 +1556,7 @@ __device__ __forceinline__ bool toi_far(const Car& c, const Poly* pa, const LWal
   b = fmaxb(b, toi_gap_bound(cy, d, dc, cx, cy, wx, wy, wl.hx, wl.hy));
   const float da = c.a - c.a0;
   if (b - fabsf(da) * R_CAR > TOI_CULL_DIST) return true;
-#if TOI_CULL2
   return toi_far_rot2(c, wl, d, da, b);
-#else
-  return false;
-#endif
 }
 
 // b2World::SolveTOI, wave-cooperative.  Box2D's loop per car: scan the contacts (a cached alpha, or a fresh
@@ -1853,21 +1582,13 @@ __device__ __forceinline__ float toi_beta(float4 s0, float4 s1, const LWall& wl,
 }
 __device__ __forceinline__ float toi_alpha(float4 s0, float4 s1, const LWall& wl, int* iters = nullptr,
                                            unsigned long long* cyc = nullptr) {
-#ifdef NASCAR_KO_TOIJOBS
-  return 1.0f;
-#endif
   int state;
   const float beta = toi_beta(s0, s1, wl, &state, iters, cyc);
   return state == TOI_TOUCHING ? fminb(s1.z + (1.0f - s1.z) * beta, 1.0f) : 1.0f;
 }
-#ifndef TOI_COOP_MANI
-#define TOI_COOP_MANI 1
-#endif
 // contact ci's b2Contact::Update inside a TOI event: from the wave's cooperative manifold when it has one
 __device__ __forceinline__ void toi_contact_update(Car& c, int ci, const LWall* W, int moff) {
-#if TOI_COOP_MANI
   if (moff + ci < MANI_JOBCAP) { contact_apply(c, ci, W, g_wave_lds[threadIdx.x >> 6].mani.res[moff + ci]); return; }
-#endif
   contact_update(c, ci, W);
 }
 __device__ inline void solve_toi(Car& c, const WallSet& S, float dt, float friction) {
@@ -1982,9 +1703,6 @@ __device__ inline void solve_toi(Car& c, const WallSet& S, float dt, float frict
         if (!(ct.flags & CT_ENABLED) || ct.toiCount > MAX_SUBSTEPS || !(ct.flags & CT_TOI)) continue;
         if (ct.toi < minAlpha) { minC = i; minAlpha = ct.toi; }
       }
-#ifdef NASCAR_KO_EVENTS
-      minC = -1;
-#endif
       if (minC < 0 || 1.0f - 10.0f * FLT_EPS < minAlpha) {
         active = false;
       } else {
@@ -2011,7 +1729,6 @@ __device__ inline void solve_toi(Car& c, const WallSet& S, float dt, float frict
     const unsigned long long tm0 = __builtin_amdgcn_s_memtime();
     if (ev) CCOUNT(c, 38, tm0 - ts3);   // scan on cached alphas + advance to the TOI pose
 #endif
-#if TOI_COOP_MANI
     if (__ballot(ev)) {   // wave-uniform
       ManiWaveLDS& M = g_wave_lds[threadIdx.x >> 6].mani;
       const int mm = ev ? c.nct : 0;
@@ -2037,7 +1754,6 @@ __device__ inline void solve_toi(Car& c, const WallSet& S, float dt, float frict
       }
       wave_lds_sync();
     }
-#endif
 #ifdef NASCAR_PROFILE
     if (ev) CCOUNT(c, 32, __builtin_amdgcn_s_memtime() - tm0);   // the wave's manifold round for this event
 #endif
@@ -2062,9 +1778,6 @@ __device__ inline void solve_toi(Car& c, const WallSet& S, float dt, float frict
           {
           CTIME_BEGIN();
           for (int i = 0; i < c.nct; ++i) {
-#ifdef NASCAR_KO_EV_CU
-            break;
-#endif
             if (n == MAX_TOI_CONTACTS) break;
             if (n == MAX_ISLAND) {   // more touching contacts than the island buffer: flag, keep going exactly-as-far-as-possible
               if (!(c.ct[i].flags & CT_ISLAND)) { c.overflow = 2; }
@@ -2082,9 +1795,7 @@ __device__ inline void solve_toi(Car& c, const WallSet& S, float dt, float frict
           float subdt = (1.0f - minAlpha) * dt;
           {
           CTIME_BEGIN();
-#ifndef NASCAR_KO_EV_ISLAND
           island_solve_toi(c, W, cidx, n, subdt, friction);
-#endif
           CTIME_END(c, 11);
           }
           {
@@ -2095,17 +1806,13 @@ __device__ inline void solve_toi(Car& c, const WallSet& S, float dt, float frict
           }
           {
           CTIME_BEGIN();
-#ifndef NASCAR_KO_EV_FIND
           find_new_contacts(c, S);
-#endif
           CTIME_END(c, 16);
           }
         }
       }
     }
-#if TOI_COOP_MANI
     wave_lds_sync();   // every owner's result reads done before the next scan's LDS writes
-#endif
 #ifdef NASCAR_PROFILE
     CCOUNT(c, 15, __builtin_amdgcn_s_memtime() - te0);   // the wave's event processing of this scan
 #endif
@@ -2121,40 +1828,18 @@ __device__ inline void b2_step(Car& c, const WallSet& S, float dt, float frictio
   const unsigned long long t0 = __builtin_amdgcn_s_memtime();
   CCOUNT(c, 1, c.nct);
 #endif
-  // NASCAR_KO_*: knockout builds for timing attribution only (a phase skipped: wrong results, never shipped)
-#ifndef NASCAR_KO_COLLIDE
   {
   CTIME_BEGIN();
   collide(c, S);
   CTIME_END(c, 23);
   }
-#endif
   PROFB(11);
-#ifndef NASCAR_KO_SOLVE
-  {
-  const bool awake = c.awake != 0;   // b2World::Solve updates the pairs of awake bodies only
   solve(c, S, dt, dtRatio, friction);
-#if BP_COOP
-  CTIME_BEGIN();
-  if (awake && c.moved) CCOUNT(c, 24, 1);
-  find_new_contacts_wave(c, S, awake);
-  CTIME_END(c, 21);
-#endif
-  }
-#endif
   PROFB(13);
 #ifdef NASCAR_PROFILE
   const unsigned long long t1 = __builtin_amdgcn_s_memtime();
 #endif
-#ifndef NASCAR_KO_TOI
-#if MODEL_PRIO == 2   // A/B: waves in SolveTOI issue ahead of co-resident waves
-  __builtin_amdgcn_s_setprio(3);
-#endif
   solve_toi(c, S, dt, friction);
-#if MODEL_PRIO == 2
-  __builtin_amdgcn_s_setprio(0);
-#endif
-#endif
 #ifdef NASCAR_PROFILE
   const unsigned long long t2 = __builtin_amdgcn_s_memtime();
   CCOUNT(c, 0, t2 - t0); (void)t1;

@@ -60,9 +60,7 @@ struct DSeg {   // per segment, float64 (src/track_generator.py TrackSegment)
 // for the bound c^2 * kq m, rounded down from the wall's exact bound (c < cmax = 2^(16 - wbits) - 1, the sentinel's
 // code, past every hit), so the codes are conservative and ascend along a list.  A ray walks its list and stops at the first entry whose bound exceeds its best hit so far: the minimum exact
 // fraction over the walls visited is the minimum over all walls, i.e. the reference's Box2D RayCast result.
-#ifndef BEAM_NB
 #define BEAM_NB 256       // direction bins (measured 64: 44.2 us, 128: 41.7, 256: 38.7, 512: 39.1) (a multiple of 16: ray i is BEAM_NB / 16 bins from ray i + 1)
-#endif
 #define BEAM_STRIDE (BEAM_NB / 16)
 // list slot of a bin: the 16 bins of one residue mod BEAM_STRIDE are adjacent, so a car's 16 rays read
 // 16 adjacent lists
@@ -87,9 +85,7 @@ struct BeamGrid {
   const uint2* head;
 };
 #define BEAM_HEAD 3
-#ifndef RAY_CHUNK
 #define RAY_CHUNK 4    // list entries past the head requested together
-#endif
 // an entry's distance bound in m (the sentinel's: beyond every hit) and its wall
 __device__ __forceinline__ float beam_bound(const BeamGrid& G, uint32_t v) {
   const uint32_t c = v >> G.wbits;
@@ -152,24 +148,14 @@ __device__ __forceinline__ int blk_env_of(const Params& P, int el, int s) {
 __device__ __forceinline__ int blk_track_of(const Params& P, int b) { return P.one_track >= 0 ? P.one_track : P.blk_track[b]; }
 // a workgroup of no track: the device-built block map's workgroups past the last track's (random-track mode); every
 // kernel returns first for them (never taken with the host-built map, whose workgroups all hold envs)
-#ifndef EMPTY_GUARD
-#define EMPTY_GUARD 1
-#endif
-__device__ __forceinline__ bool blk_empty(const Params& P, int b) { return EMPTY_GUARD && P.one_track < 0 && P.blk_track[b] < 0; }
+__device__ __forceinline__ bool blk_empty(const Params& P, int b) { return P.one_track < 0 && P.blk_track[b] < 0; }
 // The step kernels' workgroup (block-map index) of this dispatch slot.  The dispatcher deals a launch's workgroups
-// round-robin over the 8 XCDs (slot b on XCD b % 8), each with its own L2; with XCD_REMAP, each XCD takes a contiguous
+// round-robin over the 8 XCDs (slot b on XCD b % 8), each with its own L2; remapped here, each XCD takes a contiguous
 // run of the launch's workgroups instead, so the state cache lines two neighbouring workgroups share (a workgroup's
 // SoA run of cars rarely ends on a 128-B line) are fetched into one L2, not two.
-#ifndef XCD_REMAP
-#define XCD_REMAP 1
-#endif
 __device__ __forceinline__ int wg_block(const Params& P) {
-#if XCD_REMAP
   const int nb = gridDim.x, b = blockIdx.x, q = nb >> 3, r = nb & 7, x = b & 7;
   return P.blk0 + x * q + min(x, r) + (b >> 3);
-#else
-  return blockIdx.x + P.blk0;
-#endif
 }
 // BeamGrid record of the cell holding (x, y): (list base = built cell id * BEAM_NB, its chunk's first ent[] index);
 // list base -1 outside the built cells
@@ -986,9 +972,7 @@ extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 // group are dropped; surviving rays are tested per wall with the bounding-circle cull and
 // the exact b2PolygonShape::RayCast.  The result is the minimum over every wall that can
 // hit each ray, i.e. the reference's value, whatever the visiting order.
-#ifndef SENSOR_LPC
 #define SENSOR_LPC 4
-#endif
 __device__ __forceinline__ float sensor_value(float best) {   // DistanceSensor distance -> obs (src/car_env.py:946)
   double hd = best <= 1.0f ? (double)best * 250.0 : 250.0;
   float d32 = (float)hd;
@@ -1060,12 +1044,99 @@ __device__ __forceinline__ unsigned seg_ray_mask(float ax, float ay, float bx, f
   return ((m << (lo & 15)) | (m >> (16 - (lo & 15)))) & 0xFFFFu;
 }
 
+// b2PolygonShape::RayCast of one wall box for the ray p1 -> p2 (the arithmetic of sensor_kernel's inner
+// loop: same culls, same face order and f32 operations); returns min(bi, hit fraction).
+// (dx, dy): the ray direction, cull only.
+__device__ __forceinline__ float wall_cast(const float4 wa, const float4 wb, V2 p1, float p2x, float p2y, float dx,
+                                           float dy, float bi) {
+  const float rx = wa.x - p1.x, ry = wa.y - p1.y;
+  const float R = wa.z;
+  const float tc = rx * dx + ry * dy, perp = fabsf(rx * dy - ry * dx);
+  if (perp > R || tc < -R || (tc - R) > 250.0f * bi) return bi;
+  Rot q; q.s = wb.x; q.c = wb.y;
+  const float hx = wa.w, hy = wb.z;
+  if (perp > hx * fabsf(q.c * dy - q.s * dx) + hy * fabsf(q.s * dy + q.c * dx) + 0.02f) return bi;
+  const V2 l1 = rmulT(q, V(p1.x - wa.x, p1.y - wa.y));
+  // Box2D's num_f = dot(normal_f, vertex_f - l1) and den_f = dot(normal_f, d) with the box normals (0, -1), (1, 0),
+  // (0, 1), (-1, 0): the products by 0 and +-1 are dropped.  The values are the same floats except possibly the sign
+  // of a zero (0 * x + (-y) vs -y), and a zero's sign never reaches the result: den is only compared (== < > 0, a
+  // zero den selects the parallel case), and a zero num can neither lower `lower` (0 < lower * den <= 0 is false
+  // for den < 0) nor reach the returned fraction through `upper` (only compared)
+  const float n0 = l1.y - (-hy);
+  const float n1 = hx - l1.x;
+  const float n2 = hy - l1.y;
+  const float n3 = l1.x - (-hx);
+  const V2 l2 = rmulT(q, V(p2x - wa.x, p2y - wa.y));
+  const V2 dd = vsub(l2, l1);
+  float lower = 0.0f, upper = 1.0f; int index = -1; bool ok = true;
+  const float num[4] = {n0, n1, n2, n3};
+  const float den[4] = {-dd.y, dd.x, dd.y, -dd.x};
+  // Box2D's face loop as selects (no divergent branches; 166.6 -> 161.4 us/step sharded: VALU-bound walks): every
+  // face's quotient is computed and applied only where the branchy loop would have assigned it; a face after the
+  // loop's break (ok false) changes nothing
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const float n = num[f], d = den[f];
+    const float q = fdiv_cr(n, d);              // unused when d == 0
+    const bool z = d == 0.0f;
+    const bool lo = !z && d < 0.0f && n < lower * d;
+    const bool up = !z && !lo && d > 0.0f && n < upper * d;
+    const bool kill = z && n < 0.0f;
+    lower = ok && lo ? q : lower;
+    index = ok && lo ? f : index;
+    upper = ok && up ? q : upper;
+    ok = ok && !kill && !(upper < lower);
+  }
+  return (ok && index >= 0 && lower < bi) ? lower : bi;
+}
+
+// Opponent-aware sensors (nascar_set_car_visibility): b2PolygonShape::RayCast of the ray p1 -> p2 against the box of every
+// other car of car n's env, from the pass's pose records (pass A: pose[n], pass B: pose[N + n]; every writer of a pass
+// writes whole envs, so the other cars' records are valid whatever their mode words say).  Car j's box: centre the
+// record's (x, y) (the body origin), rotation b2Rot::Set of the record's float32 angle (the body's xf.q), half extents
+// CAR_HX, CAR_HY; the cast is wall_cast's, so face order, lower = 0 / upper = 1 and the f32 operations are the walls'.
+// A ray that starts inside a box gets no hit from it (index < 0).  Returns min(bi, hit fractions).
+// Two phases.  First wall_cast's first cull with the car's bounding radius (> sqrt(CAR_HX^2 + CAR_HY^2) = 2.80323, the
+// margin far above the f32 noise of the cast at <= 500 m) over every record, CAR_RAY_CHUNK records requested together
+// (independent loads: one memory latency per chunk -- one dependent load per car measured 5 us slower on the 8192 x 10
+// sensor launch, 8 per chunk no faster); run after the ray's wall walk, bi is small and most cars end there.  Then the survivors (a bit mask,
+// C <= 64): the record again, its sincosf and the cast.  The first phase culls with the wall hit, wall_cast repeats the
+// cull with the running best: both conservative, the result is the unculled minimum.  The 16 lanes of a car read the
+// same records (broadcast loads).
+#define CAR_RAY_R 2.81f
+#define CAR_RAY_CHUNK 4
 __device__ __forceinline__ float car_casts(const Params& P, int n, int pass, V2 p1, float p2x, float p2y, float dx, float dy,
-                                           float bi);
-template <int LPC, bool VIS = false>   // VIS: opponent-aware sensors (car_casts, below), after the walls
-#ifndef SENSOR_WPE
+                                           float bi) {
+  const int C = P.C;
+  const int first = (int)((unsigned)n / (unsigned)C) * C, self = n - first;
+  const float4* __restrict__ rec = P.pose + (pass == 0 ? (size_t)0 : (size_t)P.N) + first;
+  unsigned long long cand = 0ull;
+#pragma unroll 1
+  for (int j0 = 0; j0 < C; j0 += CAR_RAY_CHUNK) {
+    float2 o[CAR_RAY_CHUNK];
+#pragma unroll
+    for (int u = 0; u < CAR_RAY_CHUNK; ++u) o[u] = *(const float2*)(rec + min(j0 + u, C - 1));   // (x, y) of the record
+#pragma unroll
+    for (int u = 0; u < CAR_RAY_CHUNK; ++u) {
+      const int j = j0 + u;
+      const float rx = o[u].x - p1.x, ry = o[u].y - p1.y;
+      const float tc = rx * dx + ry * dy, perp = fabsf(rx * dy - ry * dx);
+      const bool out = perp > CAR_RAY_R || tc < -CAR_RAY_R || (tc - CAR_RAY_R) > 250.0f * bi;
+      if (j < C && j != self && !out) cand |= 1ull << (j & 63);
+    }
+  }
+  while (cand) {
+    const int j = __builtin_ctzll(cand);
+    cand &= cand - 1ull;
+    const float4 o = rec[j];
+    const Rot q = rot_set(o.z);
+    bi = wall_cast(make_float4(o.x, o.y, CAR_RAY_R, CAR_HX), make_float4(q.s, q.c, CAR_HY, 0.0f), p1, p2x, p2y, dx, dy, bi);
+  }
+  return bi;
+}
+
 #define SENSOR_WPE 6   // 80 VGPRs: all 5 464 waves of the 8192x10 bench resident at once (measured best of 4/5/6)
-#endif
+template <int LPC, bool VIS = false>   // VIS: opponent-aware sensors (car_casts), after the walls
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SENSOR_WPE))) sensor_kernel(Params P, float* obs,
                                                                                                         float* terminal_obs, int passes) {
   constexpr int CPW = BLOCK / LPC;          // cars per workgroup
@@ -1250,112 +1321,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SENS
 }
 
 // ------------------------------------------------------------------ ray_sensor_kernel: one lane per ray
-#ifndef WALL_CAST_SELECT
-#define WALL_CAST_SELECT 1   // face loop as selects: 166.6 -> 161.4 us/step sharded (VALU-bound walks, fewer divergent branches)
-#endif
-// b2PolygonShape::RayCast of one wall box for the ray p1 -> p2 (the arithmetic of sensor_kernel's inner
-// loop: same culls, same face order and f32 operations); returns min(bi, hit fraction).
-// (dx, dy): the ray direction, cull only.
-__device__ __forceinline__ float wall_cast(const float4 wa, const float4 wb, V2 p1, float p2x, float p2y, float dx,
-                                           float dy, float bi) {
-  const float rx = wa.x - p1.x, ry = wa.y - p1.y;
-  const float R = wa.z;
-  const float tc = rx * dx + ry * dy, perp = fabsf(rx * dy - ry * dx);
-  if (perp > R || tc < -R || (tc - R) > 250.0f * bi) return bi;
-  Rot q; q.s = wb.x; q.c = wb.y;
-  const float hx = wa.w, hy = wb.z;
-  if (perp > hx * fabsf(q.c * dy - q.s * dx) + hy * fabsf(q.s * dy + q.c * dx) + 0.02f) return bi;
-  const V2 l1 = rmulT(q, V(p1.x - wa.x, p1.y - wa.y));
-  // Box2D's num_f = dot(normal_f, vertex_f - l1) and den_f = dot(normal_f, d) with the box normals (0, -1), (1, 0),
-  // (0, 1), (-1, 0): the products by 0 and +-1 are dropped.  The values are the same floats except possibly the sign
-  // of a zero (0 * x + (-y) vs -y), and a zero's sign never reaches the result: den is only compared (== < > 0, a
-  // zero den selects the parallel case), and a zero num can neither lower `lower` (0 < lower * den <= 0 is false
-  // for den < 0) nor reach the returned fraction through `upper` (only compared)
-  const float n0 = l1.y - (-hy);
-  const float n1 = hx - l1.x;
-  const float n2 = hy - l1.y;
-  const float n3 = l1.x - (-hx);
-  const V2 l2 = rmulT(q, V(p2x - wa.x, p2y - wa.y));
-  const V2 dd = vsub(l2, l1);
-  float lower = 0.0f, upper = 1.0f; int index = -1; bool ok = true;
-  const float num[4] = {n0, n1, n2, n3};
-  const float den[4] = {-dd.y, dd.x, dd.y, -dd.x};
-#if WALL_CAST_SELECT
-  // the same face loop as selects (no divergent branches): every face's quotient is computed and applied only
-  // where the branchy loop would have assigned it; a face after the loop's break (ok false) changes nothing
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    const float n = num[f], d = den[f];
-    const float q = fdiv_cr(n, d);              // unused when d == 0
-    const bool z = d == 0.0f;
-    const bool lo = !z && d < 0.0f && n < lower * d;
-    const bool up = !z && !lo && d > 0.0f && n < upper * d;
-    const bool kill = z && n < 0.0f;
-    lower = ok && lo ? q : lower;
-    index = ok && lo ? f : index;
-    upper = ok && up ? q : upper;
-    ok = ok && !kill && !(upper < lower);
-  }
-#else
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    if (!ok) break;
-    if (den[f] == 0.0f) { if (num[f] < 0.0f) ok = false; }
-    else if (den[f] < 0.0f && num[f] < lower * den[f]) { lower = fdiv_cr(num[f], den[f]); index = f; }
-    else if (den[f] > 0.0f && num[f] < upper * den[f]) { upper = fdiv_cr(num[f], den[f]); }
-    if (upper < lower) ok = false;
-  }
-#endif
-  return (ok && index >= 0 && lower < bi) ? lower : bi;
-}
-
-// Opponent-aware sensors (nascar_set_car_visibility): b2PolygonShape::RayCast of the ray p1 -> p2 against the box of every
-// other car of car n's env, from the pass's pose records (pass A: pose[n], pass B: pose[N + n]; every writer of a pass
-// writes whole envs, so the other cars' records are valid whatever their mode words say).  Car j's box: centre the
-// record's (x, y) (the body origin), rotation b2Rot::Set of the record's float32 angle (the body's xf.q), half extents
-// CAR_HX, CAR_HY; the cast is wall_cast's, so face order, lower = 0 / upper = 1 and the f32 operations are the walls'.
-// A ray that starts inside a box gets no hit from it (index < 0).  Returns min(bi, hit fractions).
-// Two phases.  First wall_cast's first cull with the car's bounding radius (> sqrt(CAR_HX^2 + CAR_HY^2) = 2.80323, the
-// margin far above the f32 noise of the cast at <= 500 m) over every record, CAR_RAY_CHUNK records requested together
-// (independent loads: one memory latency per chunk -- one dependent load per car measured 5 us slower on the 8192 x 10
-// sensor launch, 8 per chunk no faster); run after the ray's wall walk, bi is small and most cars end there.  Then the survivors (a bit mask,
-// C <= 64): the record again, its sincosf and the cast.  The first phase culls with the wall hit, wall_cast repeats the
-// cull with the running best: both conservative, the result is the unculled minimum.  The 16 lanes of a car read the
-// same records (broadcast loads).
-#define CAR_RAY_R 2.81f
-#ifndef CAR_RAY_CHUNK
-#define CAR_RAY_CHUNK 4
-#endif
-__device__ __forceinline__ float car_casts(const Params& P, int n, int pass, V2 p1, float p2x, float p2y, float dx, float dy,
-                                           float bi) {
-  const int C = P.C;
-  const int first = (int)((unsigned)n / (unsigned)C) * C, self = n - first;
-  const float4* __restrict__ rec = P.pose + (pass == 0 ? (size_t)0 : (size_t)P.N) + first;
-  unsigned long long cand = 0ull;
-#pragma unroll 1
-  for (int j0 = 0; j0 < C; j0 += CAR_RAY_CHUNK) {
-    float2 o[CAR_RAY_CHUNK];
-#pragma unroll
-    for (int u = 0; u < CAR_RAY_CHUNK; ++u) o[u] = *(const float2*)(rec + min(j0 + u, C - 1));   // (x, y) of the record
-#pragma unroll
-    for (int u = 0; u < CAR_RAY_CHUNK; ++u) {
-      const int j = j0 + u;
-      const float rx = o[u].x - p1.x, ry = o[u].y - p1.y;
-      const float tc = rx * dx + ry * dy, perp = fabsf(rx * dy - ry * dx);
-      const bool out = perp > CAR_RAY_R || tc < -CAR_RAY_R || (tc - CAR_RAY_R) > 250.0f * bi;
-      if (j < C && j != self && !out) cand |= 1ull << (j & 63);
-    }
-  }
-  while (cand) {
-    const int j = __builtin_ctzll(cand);
-    cand &= cand - 1ull;
-    const float4 o = rec[j];
-    const Rot q = rot_set(o.z);
-    bi = wall_cast(make_float4(o.x, o.y, CAR_RAY_R, CAR_HX), make_float4(q.s, q.c, CAR_HY, 0.0f), p1, p2x, p2y, dx, dy, bi);
-  }
-  return bi;
-}
-
 // One ray without a beam list (car outside the cells build_beams covers): the sensor grid's wall groups
 // of the car's cell (all groups outside the grid), culled by range, by whether this ray is in the
 // group's angular mask and by the best hit so far, then wall_cast per wall.
@@ -1417,16 +1382,8 @@ __device__ __forceinline__ void quad_transpose(const float v[4], float o[4], int
 // (rays r, r + 4, r + 8, r + 12 on lane r), BLOCK / 4 cars per workgroup, the track's wall image staged in
 // LDS.  Passes and modes as sensor_kernel (pose[n]: pass A, pose[N + n]: pass B for auto-reset cars).
 // The 16 values of a car are transposed inside its lane quad and stored as 4 x 16 contiguous bytes.
-#ifndef RSENSOR_WPE
 #define RSENSOR_WPE 6   // 4 lanes per car at 6 waves/SIMD: 41.5 us (8 lanes 53.7, 2 lanes 44.3; 16 lanes 62.4)
-#endif
 #define RAY_LPC 4     // lanes per car; each lane walks the lists of rays r, r + 4, r + 8, r + 12
-#ifndef RAY_HEADS_AHEAD
-#define RAY_HEADS_AHEAD 0
-#endif
-#ifndef RAY_NO_WALK
-#define RAY_NO_WALK 0
-#endif
 // One ray's walk of its beam list (list index li, head record h = G.head[li]): the first BEAM_HEAD entries from
 // the head, the rest of the list only when all of them were walked; stops at the first entry whose distance
 // bound lies beyond the best hit.  Returns the best b2PolygonShape::RayCast fraction (2 = no hit).
@@ -1485,9 +1442,6 @@ __device__ __forceinline__ float ray_walk(const BeamGrid& G, const float4* __res
 // the sequential stop test uses), so wall_cast's min keeps the same value; results are those of ray_walk, bit for bit.
 // A wave's continuation then costs a few rounds instead of its longest list's entries one after another.
 #define BEAM_COOP_PAD 64
-#ifndef RAY_COOP_WALK
-#define RAY_COOP_WALK 1
-#endif
 // rounds of the cooperative walk before a ray still walking finishes on its own lane (ray_walk_rest).  No bundled
 // track's lists come near it; a tools build with a cap of 1 (build(): tools/build/libnascar_coop1.so) sends every long
 // walk down that path, and tests/test_gpu_sensors.py checks its values against the product build's
@@ -1496,9 +1450,7 @@ __device__ __forceinline__ float ray_walk(const BeamGrid& G, const float4* __res
 #endif
 // lanes per walking ray and round at most 64 >> RAY_COOP_LGMIN (0: up to the whole wave for a lone ray; 2: 16 lanes, 32
 // bytes of 16-bit entries per round -- fewer line fills past a short list's sentinel; DESIGN round-6 table)
-#ifndef RAY_COOP_LGMIN
 #define RAY_COOP_LGMIN 2
-#endif
 template <bool GW>
 __device__ __forceinline__ float ray_walk_coop(const BeamGrid& G, const float4* __restrict__ sw, uint32_t k, float bi, V2 p1,
                                                V2 p2, float dx, float dy) {
@@ -1611,18 +1563,7 @@ __device__ __forceinline__ void ray_lane(const Params& P, const TrackDev& T, con
     float v[RPL];
 #pragma unroll
     for (int q = 0; q < RPL; ++q) v[q] = 0.0f;
-#if RAY_HEADS_AHEAD
-    // the four rays' list heads requested together (independent 8-byte loads) before the first walk
-    BeamHead hd[RPL];
-#pragma unroll
-    for (int q = 0; q < RPL; ++q) {
-      if (base >= 0) hd[q] = beam_head(G, cell, base + slot_of(r + LPC * q));
-      else hd[q] = BeamHead{make_uint2(0u, 0u), 0u};
-    }
-#pragma unroll
-#else
 #pragma unroll 1
-#endif
     for (int q = 0; q < RPL; ++q) {
       const int i = r + LPC * q;
       double dxd, dyd;
@@ -1633,15 +1574,9 @@ __device__ __forceinline__ void ray_lane(const Params& P, const TrackDev& T, con
       const float dx = (p2.x - p1.x) * 0.004f, dy = (p2.y - p1.y) * 0.004f;   // cull only
       float bi = 2.0f;
       uint32_t kc = 0u;   // (wave-cooperative continuation: this ray's next ent[] index, 0 when its walk is done)
-      const bool coop = COOP && LPC == 16 && RAY_COOP_WALK && __ballot(1) == ~0ull;   // every lane active: wave-uniform
+      const bool coop = COOP && LPC == 16 && __ballot(1) == ~0ull;   // every lane active: wave-uniform
       if (base >= 0) {
         const int sl = slot_of(i);
-#if RAY_HEADS_AHEAD
-        bi = ray_walk<GW>(G, sw, base + sl, hd[q], p1, p2, dx, dy);
-#elif RAY_NO_WALK   // timing probe only (wrong results): the head load without the walk
-        const BeamHead h = beam_head(G, cell, base + sl);
-        bi = __uint_as_float((h.w.x & 1u) | 0x3f800000u);
-#else
 #ifdef NASCAR_PROFILE
         const BeamHead hh = beam_head(G, cell, base + sl);
         if (LPC == 16 && pass == 0) { PROFR(4); asm volatile("" :: "v"(hh.w.x)); PROFR(5); }   // end points; head loaded
@@ -1650,7 +1585,6 @@ __device__ __forceinline__ void ray_lane(const Params& P, const TrackDev& T, con
 #else
         if (LPC == 16 && coop) bi = ray_walk<GW, true>(G, sw, base + sl, beam_head(G, cell, base + sl), p1, p2, dx, dy, &kc);
         else bi = ray_walk<GW>(G, sw, base + sl, beam_head(G, cell, base + sl), p1, p2, dx, dy);
-#endif
 #endif
       } else {
         PCOUNT(9, 1);
@@ -1882,9 +1816,7 @@ __device__ __forceinline__ void model_car(const Params& P, Car& c, int n, const 
   c.thr_in = pymax(0.0, pymin(1.0, (double)a0));
   c.brk_in = pymax(0.0, pymin(1.0, (double)a1));
   c.str_in = pymax(-1.0, pymin(1.0, (double)a2));
-#ifndef NASCAR_KO_UPDATE   // knockout timing builds only (see b2_step)
   car_update_physics(P, c, n, T);
-#endif
   car_store_model(P, n, c);
   asm volatile("" ::: "memory");   // keep the model write-back ahead of the Box2D step (register pressure)
   PROF(3);
@@ -1902,16 +1834,11 @@ __device__ __forceinline__ void model_car(const Params& P, Car& c, int n, const 
 // The env step as two launches: model_kernel (actions -> Car.update_physics -> Box2D step, one lane
 // per car; its TOI code holds it at one wave per SIMD) hands the body / listener state to logic_kernel
 // (banking, disable logic, lap timer, rewards, termination, obs, auto-reset) through the state arrays.
-#ifndef MODEL_CT_LDS
-#define MODEL_CT_LDS 1      // model_kernel holds cars' contact records in LDS (CT_LDS_CAP per lane, dynamic shared memory)
-#endif
 // a lane's slots padded to an odd number of 16-byte units, so the lanes' same-record accesses spread over the banks
 #define CT_LDS_STRIDE ((CT_LDS_CAP * sizeof(DContact) / 16) % 2 ? CT_LDS_CAP * sizeof(DContact) : CT_LDS_CAP * sizeof(DContact) + 16)
-#define MODEL_CT_LDS_BYTES (MODEL_CT_LDS ? (size_t)SBLOCK * CT_LDS_STRIDE : (size_t)0)
-#ifndef MODEL_WPE
+#define MODEL_CT_LDS_BYTES ((size_t)SBLOCK * CT_LDS_STRIDE)   // model_kernel holds cars' contact records in LDS (dynamic shared memory)
 #define MODEL_WPE 2   // 2 waves/SIMD (233 VGPRs, 244 fused with the logic, no spills since the LDS islands; round 1: 1 wave/SIMD
                       // with 256 + 44 AGPRs measured 103.6 vs 100.6 us/step)
-#endif
 // policy >= 0: the actions come from device action source `policy` (policy_car, nascar_step_driven) on the
 // current obs instead of the actions buffer -- the closed-loop driver's step without a policy_kernel launch.
 // Every thread of the block calls it (it holds the segment staging barrier); lanes without a car (env < 0) skip
@@ -1939,14 +1866,10 @@ __device__ __forceinline__ void model_block(const Params& P, const void* actions
   PROF_RT(14);
   PROF_XCC(10);
   PROF(0);
-#if MODEL_PRIO == 1   // A/B: model_kernel's waves issue ahead of co-resident logic / sensor waves of other shards
-  __builtin_amdgcn_s_setprio(2);
-#endif
   // car state and action requested before the segment staging barrier (their round trips overlap the
   // staging's instead of following it: 89 -> 84 us per step)
   if (env >= 0) car_load_phys(P, n, c);
   c.pid = n;
-#if MODEL_CT_LDS
   // the car's contact records into its LDS slots (lists of up to CT_LDS_CAP; longer ones stay global): the
   // loads are issued before the staging barrier, and every b2Contact access of the step is then an LDS one
   if (env >= 0 && c.nct <= CT_LDS_CAP) {
@@ -1955,7 +1878,6 @@ __device__ __forceinline__ void model_block(const Params& P, const void* actions
     c.ct = s_ct;
     c.ct_hw = c.nct;
   }
-#endif
   // actions (BaseEnv._convert_to_internal_action / _discrete_to_continuous, np.float32)
   float tb = 0.0f, st = 0.0f;
   if (env >= 0 && policy >= 0) {
@@ -2264,9 +2186,6 @@ struct CCon {                       // one touching car pair: b2ContactVelocityC
   V2 rA[2], rB[2]; float nm[2], tm[2], vb[2], ni[2], ti[2];
 };
 #define CC_LDS_BYTES ((size_t)SBLOCK * (sizeof(CCBody) + sizeof(CCon)))
-#ifndef CC_FUSED
-#define CC_FUSED 1   // the car-car phase inside model_logic_kernel (a call; 0: the two-launch path when it is on)
-#endif
 __device__ __attribute__((noinline)) void car_contact_env(CCBody* B, CCon* K, int C, int kcap) {
   Poly box; make_box(&box, CAR_HX, CAR_HY);
   int nk = 0;
@@ -2378,15 +2297,7 @@ __global__ void __launch_bounds__(SBLOCK) car_contact_kernel(Params P) {
   car_contact_block(P, tid, el, car, env, env >= 0 ? env * C + car : 0, smem);
 }
 
-#ifndef LOGIC_WPE
-#define LOGIC_WPE 0   // 0: the compiler's choice (182 VGPRs, 2 waves/SIMD)
-#endif
-#if LOGIC_WPE
-#define LOGIC_ATTR __attribute__((amdgpu_waves_per_eu(LOGIC_WPE)))
-#else
-#define LOGIC_ATTR
-#endif
-__global__ void __launch_bounds__(SBLOCK) LOGIC_ATTR logic_kernel(Params P, float* obs, float* reward, uint8_t* car_flags,
+__global__ void __launch_bounds__(SBLOCK) logic_kernel(Params P, float* obs, float* reward, uint8_t* car_flags,
                                                       uint8_t* env_flags, int auto_reset, float* terminal_obs) {
   __shared__ LogicLDS L;
   __shared__ TrackLDS TL;
@@ -2417,14 +2328,7 @@ __global__ void __launch_bounds__(SBLOCK) LOGIC_ATTR logic_kernel(Params P, floa
 // code as the two kernels, so the results are identical (tests run both).
 struct FusedLogicLDS { LogicLDS L; TrackLDS TL; };
 // the logic half of model_logic_kernel (inlined: out of line it spilled more, 39 vs 30 VGPRs)
-#ifndef FUSED_LOGIC_NOINLINE
-#define FUSED_LOGIC_NOINLINE 0
-#endif
-#if FUSED_LOGIC_NOINLINE
-__attribute__((noinline))
-#else
 __forceinline__
-#endif
 static __device__ void fused_logic_phase(const Params& P, int tid, int el, int car, int env, int n, float* obs, float* reward,
                                          uint8_t* car_flags, uint8_t* env_flags, int auto_reset, float* terminal_obs,
                                          Car& c, double sim, int pend_in, int reason_in, const SegReg& sr) {
@@ -2457,9 +2361,7 @@ __device__ __forceinline__ void model_logic_body(const Params& P, const void* ac
   model_block<true>(P, actions, discrete, want_term, policy, seed, step, pobs, tid, env, n, c, sr);
   __syncthreads();   // the block's Box2D steps done: body state stored, contact slots written back (LDS free)
   PROF(6);           // profile builds: the fused kernel's logic half (stamp slots 6-9)
-#if CC_FUSED
   if (P.car_contact) car_contact_block(P, tid, el, car, env, n, smem);   // block-uniform; holds its own barriers
-#endif
   fused_logic_phase(P, tid, el, car, env, n, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, c, sim, pend_in,
                     reason_in, sr);
   PROF(8);
@@ -3245,10 +3147,8 @@ static void build_grids(HostTrack& t) {
 // Both are conservative, so the walk in ray_sensor_kernel visits every wall that can be the first hit.
 // Cell size: the cell's disk widens every wall's angular arc and lowers its distance bound, so smaller cells give
 // shorter walks (steady-state sensor tails; bench step 191 -> 178 / 174 / 168 / 167 us at 2 / 1.5 / 1 / 0.75 m,
-// tools/ab2.sh) at 0.2-0.5 GB of lists per track at 1 m (8-byte heads + sentinel-terminated continuations).
-#ifndef BEAM_CELL_M
+// round 4) at 0.2-0.5 GB of lists per track at 1 m (8-byte heads + sentinel-terminated continuations).
 #define BEAM_CELL_M 1.0f
-#endif
 #define BEAM_CELL_MIN 0.5f    // nascar_set_beam_cell range (heads: cell count x 4 KB; walks: longer above ~2 m)
 #define BEAM_CELL_MAX 8.0f
 static const double BEAM_BAND = 8.0;
@@ -4196,12 +4096,8 @@ static int sensor_impl() {
 // headline's 81 920 cars (41.5 vs 62 us); with 1 m cells and the sharded rollout 16 lanes measure faster there too
 // (driver's command 148.9 / 151.7 vs 158.0 / 155.2 us per step, round 4), as they did for small batches (cfg2).
 // NASCAR_RAY_LPC = 4 / 16 or nascar_set_sensor_lanes overrides.
-#ifndef RAY_LPC16_MAX_CARS
-#define RAY_LPC16_MAX_CARS (1 << 30)
-#endif
 static int ray_lpc(const NascarHandle* h) {
-  if (h->ray_lanes == 4 || h->ray_lanes == 16) return h->ray_lanes;   // nascar_set_sensor_lanes / NASCAR_RAY_LPC
-  return h->N <= RAY_LPC16_MAX_CARS ? 16 : 4;
+  return h->ray_lanes == 4 ? 4 : 16;   // nascar_set_sensor_lanes / NASCAR_RAY_LPC
 }
 // nb step-kernel workgroups from P.blk0 (each is `sub` sensor workgroups)
 // VIS: the opponent-aware instantiations (nascar_set_car_visibility); false: the kernels as they are without the extension
@@ -4304,24 +4200,6 @@ extern "C" int nascar_reset(NascarHandle* h, const uint8_t* env_mask, float* obs
   return 0;
 }
 
-static int step_impl(NascarHandle* h, const void* actions, int32_t discrete, int policy, uint64_t seed, int64_t step,
-                     float* obs, float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset,
-                     float* terminal_obs, void* stream);
-extern "C" int nascar_step(NascarHandle* h, const void* actions, int32_t discrete, float* obs, float* reward,
-                           uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs, void* stream) {
-  if (!h || !actions || !obs || !reward) return fail("null argument");
-  return step_impl(h, actions, discrete, -1, 0, 0, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
-}
-extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, float* obs, float* reward,
-                                  uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs,
-                                  void* stream) {
-  if (!h || !obs || !reward) return fail("null argument");
-  if (policy == 2 || policy == 4)
-    return fail("driven step: policy %d (MLP controllers) runs in launches of its own -- use nascar_policy_actions + nascar_step "
-                "or nascar_rollout", policy);
-  if (policy != 0 && policy != 1 && policy != 3) return fail("driven step policy must be 0, 1 or 3 (got %d)", policy);
-  return step_impl(h, nullptr, 0, policy, seed, step, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
-}
 // one env step of step-kernel workgroups [P.blk0, P.blk0 + nb) on stream s:
 // model_kernel -> logic_kernel -> sensor_kernel (pass A for every car, pass B for auto-reset cars)
 // obs_in: the observation the device driver reads (the previous step's); obs: where this step's is written
@@ -4333,7 +4211,7 @@ static int launch_step_range(NascarHandle* h, const Params& P, int nb, const voi
                              uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs,
                              hipStream_t s, int phases = PH_ALL, bool model_issued = false) {
   const bool timed = h->step_ev[0] && nb == h->nblocks;   // nascar_set_step_events: whole-grid steps only
-  if (h->fuse_ml && (CC_FUSED || !h->car_contact)) {   // model + logic in one launch (model_logic_kernel); logic is part of PH_MODEL
+  if (h->fuse_ml) {   // model + logic in one launch (model_logic_kernel); logic is part of PH_MODEL
     // Under the fused kernel the logic phase IS part of PH_MODEL's launch, so a PH_LOGIC-only request enqueues nothing:
     // only a caller that has already requested PH_MODEL for the same step and range may make it (model_issued: the
     // sharded rollout's phase-major loop, 1 << ph for ph = 0, 1, 2); anyone else gets an error, not a silently
@@ -4402,6 +4280,21 @@ static int step_impl(NascarHandle* h, const void* actions, int32_t discrete, int
                         terminal_obs, (hipStream_t)stream))
     return -1;
   return rt ? rt_after_step(h, P, ef, obs, (hipStream_t)stream) : 0;
+}
+extern "C" int nascar_step(NascarHandle* h, const void* actions, int32_t discrete, float* obs, float* reward,
+                           uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs, void* stream) {
+  if (!h || !actions || !obs || !reward) return fail("null argument");
+  return step_impl(h, actions, discrete, -1, 0, 0, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
+}
+extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, float* obs, float* reward,
+                                  uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs,
+                                  void* stream) {
+  if (!h || !obs || !reward) return fail("null argument");
+  if (policy == 2 || policy == 4)
+    return fail("driven step: policy %d (MLP controllers) runs in launches of its own -- use nascar_policy_actions + nascar_step "
+                "or nascar_rollout", policy);
+  if (policy != 0 && policy != 1 && policy != 3) return fail("driven step policy must be 0, 1 or 3 (got %d)", policy);
+  return step_impl(h, nullptr, 0, policy, seed, step, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
 }
 
 // Sharded rollout: the workgroups split into S contiguous ranges (shards of whole envs), each stepped `steps`
@@ -4789,9 +4682,6 @@ extern "C" int nascar_set_state(NascarHandle* h, const void* src, void* stream) 
   return 0;
 }
 
-static void launch_actor(NascarHandle* h, int n, const float* obs, float* actions, void* stream);
-static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int64_t step, const float* obs, float* act,
-                        hipStream_t s);
 extern "C" int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, const float* obs,
                                      float* actions, void* stream) {
   if (!h || !actions) return fail("null argument");

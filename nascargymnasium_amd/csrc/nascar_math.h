@@ -81,10 +81,7 @@ __host__ __device__ __forceinline__ uint32_t inv_pio4(int i) {
 }
 // |y| >= 120: rare (wound-up angles).  Out of line on the device: inlined into every b2Rot::Set it was ~15 KB of
 // model_kernel's code for a path almost never taken.
-#ifndef SINCOS_LARGE_INLINE
-#define SINCOS_LARGE_INLINE 0
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && !SINCOS_LARGE_INLINE
+#ifdef __HIP_DEVICE_COMPILE__
 __attribute__((noinline))
 #endif
 __host__ __device__ inline double reduce_large(uint32_t xi, int* np) {
@@ -107,17 +104,7 @@ __host__ __device__ inline double reduce_large(uint32_t xi, int* np) {
 // glibc sinf and cosf (sysdeps/ieee754/flt-32/s_sinf.c, s_cosf.c; FMA variant) of the same argument in one
 // pass: both share the range reduction, and each result is bit-identical to the separate call (the same
 // operations on the same values).  b2Rot::Set calls sinf then cosf.
-#ifndef SINCOS_NOINLINE
-#define SINCOS_NOINLINE 0   // A/B: one out-of-line copy of b2Rot::Set's sincosf instead of one per call site
-#endif
-#ifndef SINCOS_V2
-#define SINCOS_V2 1
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && SINCOS_NOINLINE
-__attribute__((noinline))
-#endif
 __host__ __device__ inline void glibc_sincosf(float y, float* sp, float* cp) {
-#if SINCOS_V2
   // One straight-line path for |y| < 120 (the only rare branch is glibc's reduce_large): glibc's |y| < pi/4 path is
   // reduce_fast's n = 0 case (x - 0 * pi/2 == x exactly, sign +1, first table row), and both polynomials are
   // evaluated side by side and assigned by the quadrant's parity (glibc evaluates the same two polynomials on the
@@ -144,32 +131,6 @@ __host__ __device__ inline void glibc_sincosf(float y, float* sp, float* cp) {
   const bool odd = n & 1, tiny = t < top12(0x1p-12f);
   *sp = tiny ? y : (odd ? pc : ps);
   *cp = tiny ? 1.0f : (odd ? ps : pc);
-#else
-  double x = y;
-  int n = 0, row = 0;
-  double sgn = 1.0;
-  const float pio4 = 0x1.921FB6p-1f;
-  if (top12(y) < top12(pio4)) {
-    if (top12(y) < top12(0x1p-12f)) { *sp = y; *cp = 1.0f; return; }
-    double x2 = x * x;
-    *sp = sc_poly(x, x2, 0, 0);
-    *cp = sc_poly(x, x2, 1, 0);
-    return;
-  } else if (top12(y) < top12(120.0f)) {
-    x = reduce_fast(x, &n);
-    sgn = ((n + 1) & 2) ? -1.0 : 1.0;   // {1, -1, -1, 1}[n & 3]
-    row = n & 2;
-  } else {
-    uint32_t xi = f_as_u(y);
-    int sign = xi >> 31;
-    x = reduce_large(xi, &n);
-    sgn = ((n + sign + 1) & 2) ? -1.0 : 1.0;
-    row = (n + sign) & 2;
-  }
-  const double xs = x * sgn, x2 = x * x;
-  *sp = sc_poly(xs, x2, n, row);
-  *cp = sc_poly(xs, x2, n ^ 1, row);
-#endif
 }
 
 // Python float64 helpers

@@ -1,13 +1,11 @@
 #!/bin/bash
-# A/B session: per-kernel mean durations from one saved steady state (tools/kt_ss.sh, KT_LIBS), the driver's
-# command alternated over libraries (tools/ab3.sh, AB3_LIBS, ROUNDS), the driver's command at S env shards on S hardware
-# queues (QUEUES="4 6 8", ROUNDS), a kernel-trace timeline of the sharded rollout (TRACE=1, tools/ro_trace.sh), then GPU
-# tests (TESTS, pytest paths/args).
+# A/B session: per-kernel mean durations from one saved steady state (tools/kt_ss.sh, KT_LIBS), the driver's command
+# at S env shards on S hardware queues (QUEUES="4 6 8", ROUNDS), a kernel-trace timeline of the sharded rollout
+# (TRACE=1, tools/ro_trace.sh), then GPU tests (TESTS, pytest paths/args).
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT="$GRAFT_REPO_ROOT/gpurun_out"; mkdir -p "$OUT"
 stop() { rc=$1; echo "$2 rc=$rc"; if [ "$rc" -ge 124 ]; then exit "$rc"; fi; }
 if [ -n "$KT_LIBS" ]; then bash tools/kt_ss.sh $KT_LIBS > "$OUT/ab_kt.log" 2>&1; stop $? kt; cat "$OUT/ab_kt.log"; fi
-if [ -n "$AB3_LIBS" ]; then ROUNDS=${ROUNDS:-3} bash tools/ab3.sh $AB3_LIBS > "$OUT/ab_ab3.log" 2>&1; stop $? ab3; cat "$OUT/ab_ab3.log"; fi
 if [ -n "$QUEUES" ]; then
   for r in $(seq 1 ${ROUNDS:-2}); do for q in $QUEUES; do
     GPU_MAX_HW_QUEUES=$q timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary \

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box A/B of library builds (tools/build/libnascar_<variant>.so, VARIANTS="a b ..."): per variant the step
 # kernels' mean dispatch times (rocprofv3 --stats), their HBM bytes per car (FETCH_SIZE x2 + WRITE_SIZE), and the
-# driver's command twice, all from one saved steady state
+# driver's command twice, all from one saved steady state; the logs and rocprofv3 tables stay under $OUT
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT="$GRAFT_REPO_ROOT/gpurun_out/ablib"; rm -rf "$OUT"; mkdir -p "$OUT"
 stop() { rc=$1; echo "$2 rc=$rc"; if [ "$rc" -ge 124 ]; then exit "$rc"; fi; }
@@ -23,4 +23,3 @@ for v in ${VARIANTS:-base xcd}; do
     echo "$v drv$r $(grep -o '"ms_per_step": [0-9.]*' "$OUT/drv${v}_$r.log" | head -1)"
   done
 done
-python3 "$GRAFT_REPO_ROOT/tools/ab_lg_summary.py" "$OUT"
