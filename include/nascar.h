@@ -122,7 +122,8 @@ int nascar_step(NascarHandle* h, const void* actions, int32_t discrete, float* o
 /* nascar_step with the actions of device action source `policy` (0, 1, 3: see nascar_policy_actions) computed on
  * the current obs inside the step launch -- one closed-loop driver step (game/control drivers' loop) without a
  * separate action launch; identical results to nascar_policy_actions(policy, seed, step) + nascar_step.  Policies 2
- * and 4 (the MLP controllers) are not available here: use nascar_policy_actions + nascar_step, or nascar_rollout. */
+ * and 4 (the MLP controllers) and 5 (the genome drivers) are not available here: use nascar_policy_actions +
+ * nascar_step, or nascar_rollout. */
 int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, float* obs, float* reward,
                        uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs, void* stream);
 
@@ -138,7 +139,9 @@ int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed, int64_t s
  *            track's workgroups in order); 4 the field of nascar_set_car_controllers (sharded rollout only, as
  *            policy 2: each shard runs the field on its own envs, one shard when the envs do not sit in one track's
  *            workgroups in order or random tracks are on; streams = 0 fails, and under nascar_set_rollout_pipe the
- *            streams setting applies)
+ *            streams setting applies); 5 the genome drivers of nascar_set_genomes (sharded rollout only: each shard
+ *            runs the driver on the cars of its own workgroups, whatever the tracks; streams = 0 and the pipelined
+ *            rollout fail, as does a handle without a genome table)
  *   obs:     [E*C*38] float32, in: the current observation, out: the last step's
  *   traj & NASCAR_TRAJ_RECORDS: reward [steps][E*C], car_flags [steps][E*C], env_flags [steps][E] (per-step records);
  *   traj == 0: reward [E*C], car_flags [E*C], env_flags [E] hold the last step's values.
@@ -216,11 +219,14 @@ int nascar_set_step_events(NascarHandle* h, void* const* events, int32_t n);
 int nascar_get_info(NascarHandle* h, double* info, void* stream);
 
 /* BUILD-ONLY EXTENSION, no reference counterpart (each reference car has its own b2World, so cars never touch):
- * enable != 0 makes the cars of an env collide -- staggered start grid (rows of 2, 8 m apart), and after each
- * Box2D step the env's touching car pairs (b2CollidePolygons manifolds of the car boxes, 1-2 points each) are solved
- * with b2ContactSolver's sequential impulses for two dynamic bodies: 6 velocity iterations of friction (mixed
- * coefficient 0.7) then normal impulses, restitution 0.1 above Box2D's 1 m/s velocity threshold, applied to both cars'
- * linear and angular velocity, after (not interleaved with) each car's wall island, without warm start or position
+ * enable != 0 makes the cars of an env collide -- staggered start grid (rows of 2, 8 m apart), and after the cars'
+ * Box2D steps the env's car pairs within two circumradii are solved with Box2D's own contact algorithms for two dynamic
+ * bodies: b2CollidePolygons manifolds of the car boxes (1-2 clip points, face normal, world points from
+ * b2WorldManifold), then b2ContactSolver's sequential impulses -- per velocity iteration (6) and contact the tangent
+ * impulses clamped by friction x normal impulse, then the accumulated normal impulses clamped at >= 0, with the angular
+ * terms in the normal / tangent masses; fixture mixing of two car fixtures (friction sqrt(0.7 * 0.7), restitution
+ * max(0.1, 0.1) as a velocity bias below -1 m/s), applied to both cars' linear and angular velocity.  Solved after (not
+ * interleaved with) each car's wall island, point by point (no 2-point block solver), without warm start or position
  * correction.  The normal impulses count in the cars' collision impulse (damage / impact disables).  Default 0
  * (reference behaviour); parity runs with 0.  Takes effect from the next reset (start grid) and step. */
 int nascar_set_car_contact(NascarHandle* h, int32_t enable);
@@ -265,7 +271,10 @@ int nascar_set_state(NascarHandle* h, const void* src_device, void* stream);
  *             which produces exactly what policy 0, 1 or 3 produces for that car at the same (seed, step), the rule
  *             driver's per-car control state included; slots driven by a controller leave that state untouched.  One
  *             launch per distinct (h1, h2, activation) among the field's controllers plus one for the built-in slots,
- *             however many controllers are loaded.  Fails without a table.  actions 8-byte aligned. */
+ *             however many controllers are loaded.  Fails without a table.  actions 8-byte aligned.
+ *   policy 5: the genome driver -- every car runs BaseController._fallback_control with its constants replaced by the
+ *             car's 12 genes (nascar_set_genomes), one launch of its own (genome_policy_kernel); it shares the per-car
+ *             control state with policies 1 and 3.  Fails without a genome table. */
 int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, const float* obs,
                           float* actions, void* stream);
 
@@ -311,7 +320,9 @@ int nascar_actor_forward(NascarHandle* h, const float* obs, int32_t n, float* ac
  * nascar_set_car_controllers: ctrl is a host array [C]: the car in slot c of every env is driven by ctrl[c], a
  *   controller id or one of the built-in sources below; NULL clears the table.  The table is what policy 4 ("the
  *   field") of nascar_policy_actions and nascar_rollout runs; an id that was never returned by nascar_add_controller,
- *   or a negative value other than the three below, is an error. */
+ *   or a negative value other than the four below, is an error.  NASCAR_CTRL_GENOME is accepted once a genome table
+ *   is set (nascar_set_genomes first; without one the id is unknown, and a table cleared later fails the field's next
+ *   run); the slot produces exactly what policy 5 produces for that car, sharing the rule sources' control state. */
 typedef struct NascarMlp {
     int32_t obs_dim, h1, h2, act_dim;
     int32_t activation;      /* 0 ReLU, 1 Tanh */
@@ -321,10 +332,50 @@ typedef struct NascarMlp {
 #define NASCAR_CTRL_RULE (-1)      /* policy 1 */
 #define NASCAR_CTRL_UNIFORM (-2)   /* policy 0 */
 #define NASCAR_CTRL_NOISY (-3)     /* policy 3 */
+#define NASCAR_CTRL_GENOME (-4)    /* policy 5: the slot's cars run their genomes (nascar_set_genomes) */
 int nascar_check_controller(const NascarMlp* mlp);
 int nascar_add_controller(NascarHandle* h, const NascarMlp* mlp);
 int nascar_controller_forward(NascarHandle* h, int32_t id, const float* obs, int32_t n, float* actions, void* stream);
 int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl);
+
+/* Genome drivers: the rule driver of the reference's genetic trainer (game/control/genetic_controller.py,
+ * learn/genetic_trainer.py), one genome per car.  GeneticController.control cannot run as written (its line 81 reads an
+ * attribute that is defined nowhere, and the trainer turns the exception into fitness -1000), so the semantics are those
+ * of the class's docstring -- BaseController._fallback_control (game/control/base_controller.py:64-103) with its
+ * constants replaced by genes, i.e. control() without lines 81-82:
+ *   if last_forward >= forward: speed_limit = forward * g[10]      if last_forward < forward: speed_limit = 1.0
+ *   if speed < speed_limit * g[0]: tb += g[2]                      if speed > speed_limit * g[1]: tb -= g[3]
+ *   if r > l: steering = (1 - l/r) * g[4]   elif l > r: steering = ((1 - r/l) * -1) * g[4]   else: steering *= g[6]
+ *   if abs(steering) > g[7]: tb *= g[5];    both clamped to [-1, 1];    last_forward = forward
+ * in the order of GeneticController.default_genome; g[8], g[9] and g[11] are carried and unused (only the omitted lines
+ * read 8 and 9, nothing reads 11).  NumPy 2 promotion: g[0], g[1], g[4], g[6], g[7], g[10] meet float32 values and are
+ * rounded to float32 first; g[2], g[3], g[5] meet throttle_brake, a Python float, and stay float64.  A steering that
+ * the clamp saturated is the Python int +-1, and stays a float64 Python number through the exact left / right ties that
+ * follow it; the table keeps that flag per car.  The genome (0.95, 1.05, 0.1, 0.1, 1, 0.5, 0.9, 0.25, 1, 1, 1, 0.3)
+ * reproduces policy 1 bit for bit.
+ * nascar_set_genomes: genomes is a host array [E*C][12] float64 (NULL clears the table), copied to a device table
+ *   outside the state arena (nascar_state_bytes and the snapshot do not change) by an upload ordered on `stream`; every
+ *   gene must be finite.  A new table is a new set of controllers: it also zeroes every car's control state (the state
+ *   the rule sources share, as GeneticController.__init__ starts from a zero control_state) and the per-car
+ *   Python-number flags. */
+int nascar_set_genomes(NascarHandle* h, const double* genomes, void* stream);
+
+/* On-device fitness accumulators: what the trainer's evaluation loop gathers per individual from rewards[i] and
+ * info['cars'][i] after every step (learn/genetic_trainer.py:253-285), in float64.
+ * nascar_set_fitness: enable != 0 allocates (first time) and zeroes the per-car accumulators and a per-env "ended"
+ *   byte, on `stream`; 0 stops the accumulation.  While enabled, every step of nascar_step / nascar_step_driven and of the
+ *   sharded nascar_rollout enqueues fitness_kernel after its sensor launch (per shard in the rollout).  For an env that
+ *   has not ended, per car: total_reward += (double)reward; max_speed = max(max_speed, speed) with the speed of
+ *   nascar_get_info; distance += speed * (1.0 / 60.0); time_on_track += 1.0 / 60.0 when on track; steps += 1;
+ *   lap_completed and lap_time = last_lap_time at the first step with lap_count > 0 (the trainer's own lap-time lines
+ *   leave it None for ever; this is their evident intent); disabled_at_step = steps at the first step that left the car
+ *   disabled.  The step whose env flags carry terminated or truncated is included, then the env's cars stop
+ *   accumulating.  Needs auto_reset = 0 (CarEnv.step keeps stepping a finished env, and so does this engine); steps
+ *   with auto_reset, the fused and the pipelined rollout and random-track mode fail while it is on.  Off by default.
+ * nascar_get_fitness: out is a device buffer [E*C][8] float64: total_reward, distance_traveled, max_speed,
+ *   time_on_track, lap_completed, lap_time (NaN: none), steps, disabled_at_step (-1: never). */
+int nascar_set_fitness(NascarHandle* h, int32_t enable, void* stream);
+int nascar_get_fitness(NascarHandle* h, double* out, void* stream);
 
 /* Test hook: the device re-implementation of glibc sinf/cosf used for b2Rot::Set
  * (device pointers, n floats).  Parity tests compare it with the host libm. */

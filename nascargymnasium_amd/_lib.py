@@ -40,7 +40,12 @@ class NascarMlp(ctypes.Structure):
                [(n, ctypes.POINTER(ctypes.c_float)) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
 
 
-CTRL_BUILTIN = {"rule": -1, "uniform": -2, "noisy": -3}   # NASCAR_CTRL_RULE / _UNIFORM / _NOISY
+CTRL_BUILTIN = {"rule": -1, "uniform": -2, "noisy": -3, "genome": -4}   # NASCAR_CTRL_RULE / _UNIFORM / _NOISY / _GENOME
+# nascar_get_fitness rows (include/nascar.h): the metrics of learn/genetic_trainer.py:211-222 plus the car's disable step
+FITNESS_FIELDS = ["total_reward", "distance_traveled", "max_speed", "time_on_track", "lap_completed", "lap_time",
+                  "steps", "disabled_at_step"]
+N_FITNESS = len(FITNESS_FIELDS)
+N_GENES = 12
 
 
 class NascarConfig(ctypes.Structure):
@@ -146,6 +151,12 @@ def lib():
     L.nascar_controller_forward.restype = ctypes.c_int
     L.nascar_set_car_controllers.argtypes = [vp, ctypes.POINTER(i32)]
     L.nascar_set_car_controllers.restype = ctypes.c_int
+    L.nascar_set_genomes.argtypes = [vp, d_p, vp]
+    L.nascar_set_genomes.restype = ctypes.c_int
+    L.nascar_set_fitness.argtypes = [vp, i32, vp]
+    L.nascar_set_fitness.restype = ctypes.c_int
+    L.nascar_get_fitness.argtypes = [vp, vp, vp]
+    L.nascar_get_fitness.restype = ctypes.c_int
     L.nascar_set_step_events.argtypes = [vp, ctypes.POINTER(vp), i32]
     L.nascar_set_step_events.restype = ctypes.c_int
     L.nascar_debug_sincosf.argtypes = [vp, vp, vp, i32, vp]
@@ -186,6 +197,7 @@ EXPORTED = ["nascar_create", "nascar_destroy", "nascar_last_error", "nascar_add_
             "nascar_reset", "nascar_step", "nascar_step_driven", "nascar_rollout", "nascar_get_info", "nascar_set_perf_history", "nascar_set_car_contact", "nascar_set_car_visibility", "nascar_get_car_visibility", "nascar_set_rollout_streams", "nascar_get_rollout_streams", "nascar_set_rollout_pipe", "nascar_rollout_pipe_status", "nascar_set_envs_per_block", "nascar_get_envs_per_block", "nascar_set_sensor_lanes", "nascar_set_sensor_block", "nascar_set_beam_cell", "nascar_set_fused_logic", "nascar_get_fused_logic", "nascar_state_bytes", "nascar_get_state",
             "nascar_set_state", "nascar_policy_actions", "nascar_set_step_events", "nascar_set_actor", "nascar_set_actor_precision", "nascar_actor_forward",
             "nascar_check_controller", "nascar_add_controller", "nascar_controller_forward", "nascar_set_car_controllers",
+            "nascar_set_genomes", "nascar_set_fitness", "nascar_get_fitness",
             "nascar_debug_sincosf", "nascar_debug_f64math", "nascar_debug_toi", "nascar_debug_collide", "nascar_debug_sensors", "nascar_track_draw", "nascar_set_random_tracks",
             "nascar_get_env_tracks", "nascar_vec_post", "nascar_check_actions", "nascar_set_track_cache",
             "nascar_prebuild_track", "nascar_debug_block_map"]

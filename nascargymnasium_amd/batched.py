@@ -295,8 +295,10 @@ class BatchedCarEnv:
                 trajectory: bool = False, out=None, obs_trajectory: bool = False):
         """`steps` env steps in one call (sharded over streams, or one fused launch: set_rollout_streams), actions
         from device action source `policy` (0 uniform, 1 rule driver, 2 the SAC actor -- sharded only, 3 noisy rule
-        driver, 4 the field of per-car controllers, set_car_controllers -- sharded only) on the previous observation; equals `steps` x (policy_actions(policy, seed, step0 + k) +
-        step(..., auto_reset)).  Returns (obs, reward, car_flags, env_flags): the last step's, or with
+        driver, 4 the field of per-car controllers, set_car_controllers -- sharded only, 5 the genome drivers,
+        set_genomes -- sharded only, not with set_rollout_pipe) on the previous observation; equals `steps` x
+        (policy_actions(policy, seed, step0 + k) + step(..., auto_reset)).  With set_fitness on, every step also updates
+        the per-car fitness accumulators (auto_reset must be False).  Returns (obs, reward, car_flags, env_flags): the last step's, or with
         trajectory=True the per-step records [steps, E, C] / [steps, E] (obs the last step's).  obs_trajectory=True
         (with trajectory=True, sharded rollout only) also records every step's observation: obs [steps + 1, E, C, 38],
         record 0 the observation before the rollout, record k + 1 the one after step k (a learner's rollout buffer,
@@ -428,8 +430,8 @@ class BatchedCarEnv:
 
     def set_car_controllers(self, ctrl=None):
         """The field: the car in slot c of every env is driven by ctrl[c] -- a controller id from add_controller, or
-        "rule" (policy 1), "uniform" (policy 0), "noisy" (policy 3) -- as the reference's race modes build one controller
-        per car (game/competition.py:150-212).  policy_actions(4) and rollout(4, ...) then run it.  None clears it."""
+        "rule" (policy 1), "uniform" (policy 0), "noisy" (policy 3), "genome" (policy 5: the slot's cars run their genomes
+        of set_genomes, which comes first) -- as the reference's race modes build one controller per car (game/competition.py:150-212).  policy_actions(4) and rollout(4, ...) then run it.  None clears it."""
         if ctrl is None:
             _lib.check(self.L.nascar_set_car_controllers(self.h, None))
             return
@@ -446,9 +448,45 @@ class BatchedCarEnv:
         arr = (ctypes.c_int32 * self.C)(*codes)
         _lib.check(self.L.nascar_set_car_controllers(self.h, arr))
 
+    # ------------------------------------------------------------------ genome drivers and on-device fitness (policy 5)
+    FITNESS_FIELDS = _lib.FITNESS_FIELDS
+
+    def set_genomes(self, genomes=None):
+        """One 12-gene genome per car for the genome driver (policy 5, and "genome" slots of set_car_controllers): an
+        array [E, C, 12] or [E * C, 12] of Python-float (float64) genes in GeneticController.default_genome's order
+        (nascargymnasium_amd.genetic.GENOME_NAMES); None clears the table.  The driver is
+        BaseController._fallback_control with its constants replaced by the genes (include/nascar.h).  Every gene
+        must be finite.  The upload is ordered on the current stream."""
+        if genomes is None:
+            _lib.check(self.L.nascar_set_genomes(self.h, None, _stream()))
+            return
+        g = np.ascontiguousarray(np.asarray(genomes, dtype=np.float64))
+        if g.shape not in ((self.E, self.C, _lib.N_GENES), (self.N, _lib.N_GENES)):
+            raise ValueError(f"genomes must be [{self.E}, {self.C}, {_lib.N_GENES}] or [{self.N}, {_lib.N_GENES}], "
+                             f"got {tuple(g.shape)}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.nascar_set_genomes(self.h, g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _stream()))
+
+    def set_fitness(self, enable: bool = True):
+        """On-device fitness accumulators (learn/genetic_trainer.py:253-285 per car, float64): while enabled, every
+        `step` / `step_driven` and every step of the sharded `rollout` adds the step's reward, speed, distance, time on
+        track, lap and disable records of each car whose env has not ended; an env's terminal step is counted, then its
+        cars freeze.  Enabling (again) zeroes them.  Steps must run with auto_reset=False while it is on."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.nascar_set_fitness(self.h, int(bool(enable)), _stream()))
+
+    def fitness(self) -> torch.Tensor:
+        """The accumulators as an [E, C, 8] float64 device tensor (fields: FITNESS_FIELDS; lap_time NaN without a lap,
+        disabled_at_step -1 for a car that was never disabled)."""
+        out = torch.empty(self.E, self.C, _lib.N_FITNESS, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.nascar_get_fitness(self.h, _ptr(out), _stream()))
+        return out
+
     def policy_actions(self, policy: int, seed: int = 0, step: int = 0, obs: Optional[torch.Tensor] = None):
         """device-generated actions: 0 uniform U[-1,1]^2, 1 BaseController fallback driver, 2 the SAC actor, 3 the noisy
-        rule driver, 4 the field of per-car controllers (set_car_controllers)."""
+        rule driver, 4 the field of per-car controllers (set_car_controllers), 5 the genome drivers (set_genomes: the
+        rule driver with per-car evolved constants; shares the rule driver's per-car state)."""
         o = self.obs if obs is None else obs
         with torch.cuda.device(self.device):
             _lib.check(self.L.nascar_policy_actions(self.h, int(policy), int(seed), int(step), _ptr(o),

@@ -1795,10 +1795,68 @@ __global__ void field_policy_kernel(int n0, int n1, int C, FieldCodes F, uint64_
   const int n = n0 + blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= n1) return;
   const int code = F.code[n % C];
-  if (code >= 0) return;
+  if (code >= 0 || code == NASCAR_CTRL_GENOME) return;   // genome slots: genome_policy_kernel
   float a0, a1;
   policy_car(code == NASCAR_CTRL_RULE ? 1 : code == NASCAR_CTRL_UNIFORM ? 0 : 3, seed, step, n, obs, ctl, a0, a1);
   act[2 * n] = a0; act[2 * n + 1] = a1;
+}
+
+// Genome driver (policy 5, NASCAR_CTRL_GENOME): BaseController._fallback_control with its constants replaced by the
+// car's 12 genes -- GeneticController.control (game/control/genetic_controller.py:64-119) without its lines 81-82,
+// which cannot run (line 81 reads an attribute that is defined nowhere).  Gene order: GeneticController.default_genome;
+// genes 8, 9 and 11 are carried and unused.  NumPy 2 promotion as policy_car keeps it: a gene that meets a float32
+// value (0, 1, 4, 6, 7, 10) is rounded to float32 first, one that meets throttle_brake, a Python float (2, 3, 5), stays
+// float64.  New against policy 1: with g[4] > 1 the steering can leave [-1, 1], and max(min(steering, 1), -1) then
+// returns the Python int +-1; on a following exact left / right tie steering *= g[6] is a float64 product and
+// abs(steering) > g[7] a float64 comparison, until a step that is no tie makes the steering float32 again.  py_steer of
+// the car's record says that its steering (ctl[4n + 1], then a full float64) is such a Python number.
+// The driver shares ctl[4n ..] with policy 1 / 3; the identity genome reproduces policy 1 bit for bit.
+struct alignas(16) GenomeRec { double g[12]; unsigned long long py_steer, pad; };
+// one lane per car.  slot0 < 0: the cars [n0, n1) directly (nascar_policy_actions, the field's env range);
+// slot0 >= 0: the cars of the block map's env slots [slot0, slot0 + nslot) (a shard of the sharded rollout, whose envs
+// need not be contiguous); slots: bit c set = car slot c is driven (all ones: policy 5)
+__global__ void __launch_bounds__(256) genome_policy_kernel(Params P, int slot0, int nslot, int n0, int n1, uint64_t slots,
+                                                            const float* obs, float* act, double* ctl, GenomeRec* rec) {
+  const int i = blockIdx.x * 256 + threadIdx.x, C = P.C;
+  int n;
+  if (slot0 < 0) {
+    n = n0 + i;
+    if (n >= n1) return;
+  } else {
+    const int sl = i / C, car = i - sl * C, s = slot0 + sl;
+    if (sl >= nslot || blk_empty(P, s / P.epb)) return;
+    const int env = blk_env_of(P, 0, s);
+    if (env < 0) return;
+    n = env * C + car;
+  }
+  if (!((slots >> (n % C)) & 1)) return;
+  const GenomeRec G = ldg(rec + n);
+  const float g0 = (float)G.g[0], g1 = (float)G.g[1], g4 = (float)G.g[4], g6 = (float)G.g[6], g7 = (float)G.g[7],
+              g10 = (float)G.g[10];
+  const float* o = obs + (size_t)n * 38;
+  double* s = ctl + 4 * (size_t)n;   // throttle_brake, steering, last_forward, speed_limit (as policy_car)
+  const float fwd = o[22], spd = o[4];
+  const float last = (float)s[2];
+  float lim = (float)s[3];
+  double tb = s[0], st = s[1];
+  if (last >= fwd) lim = fwd * g10;
+  if (last < fwd) lim = 1.0f;
+  if (spd < lim * g0) tb += G.g[2];
+  if (spd > lim * g1) tb -= G.g[3];
+  const float r = o[22 + 15], l = o[22 + 1];
+  const bool was_py = G.py_steer != 0;
+  bool py = false;   // the steering is a Python int / float (float64), not a numpy float32
+  if (r > l) st = (double)((1.0f - (l / r)) * g4);
+  else if (l > r) st = (double)(((1.0f - (r / l)) * -1.0f) * g4);
+  else if (was_py) { st = st * G.g[6]; py = true; }
+  else st = (double)((float)st * g6);
+  if (py ? fabs(st) > G.g[7] : fabsf((float)st) > g7) tb *= G.g[5];
+  tb = tb > 1.0 ? 1.0 : tb;  tb = tb < -1.0 ? -1.0 : tb;            // max(min(tb, 1), -1)
+  if (st > 1.0) { st = 1.0; py = true; }                              // min(steering, 1) returns the int 1
+  if (st < -1.0) { st = -1.0; py = true; }
+  s[0] = tb; s[1] = st; s[2] = fwd; s[3] = lim;
+  if (py != was_py) rec[n].py_steer = py;
+  act[2 * n] = (float)tb; act[2 * n + 1] = (float)st;
 }
 
 
@@ -2701,6 +2759,17 @@ __global__ void __launch_bounds__(SBLOCK) reset_kernel(Params P, const uint8_t* 
   }
 }
 
+// The info fields that the on-device fitness accumulators read too (fitness_kernel): one definition of how each is
+// taken from the car's state, shared with info_kernel
+struct InfoCore { double speed, on_track, last_lap; int laps, disabled; };
+__device__ __forceinline__ InfoCore info_core(const WallSet& S, const Car& c) {
+  InfoCore r;
+  r.speed = (double)vlen(c.v);
+  r.on_track = query_on_wall(S, c.xf.p.x, c.xf.p.y, 0.5) ? 0.0 : 1.0;
+  r.last_lap = c.lt_has_last ? c.lt_last : NAN;
+  r.laps = c.lt_laps; r.disabled = c.disabled;
+  return r;
+}
 __global__ void __launch_bounds__(SBLOCK) info_kernel(Params P, double* info) {
   const int tid = threadIdx.x, C = P.C;
   const int el = tid / C, car = tid - el * C;
@@ -2713,13 +2782,14 @@ __global__ void __launch_bounds__(SBLOCK) info_kernel(Params P, double* info) {
   Car c;
   car_load(P, n, c);
   double* o = info + (size_t)n * N_INFO;
+  const InfoCore ic = info_core(S, c);
   o[INFO_X] = c.xf.p.x; o[INFO_Y] = c.xf.p.y; o[INFO_VX] = c.v.x; o[INFO_VY] = c.v.y; o[INFO_ANGLE] = c.a; o[INFO_OMEGA] = c.w;
-  o[INFO_SPEED] = (double)vlen(c.v); o[INFO_LAP_COUNT] = c.lt_laps;
-  o[INFO_LAST_LAP] = c.lt_has_last ? c.lt_last : NAN; o[INFO_BEST_LAP] = c.lt_has_best ? c.lt_best : NAN;
+  o[INFO_SPEED] = ic.speed; o[INFO_LAP_COUNT] = ic.laps;
+  o[INFO_LAST_LAP] = ic.last_lap; o[INFO_BEST_LAP] = c.lt_has_best ? c.lt_best : NAN;
   o[INFO_IS_TIMING] = c.lt_timing; o[INFO_CUR_LAP_TIME] = c.lt_cur; o[INFO_LAP_DIST] = c.lt_dist;
-  o[INFO_HAS_CROSSED] = c.lt_crossed; o[INFO_DISABLED] = c.disabled; o[INFO_CUM_REWARD] = c.cum_reward_info;
+  o[INFO_HAS_CROSSED] = c.lt_crossed; o[INFO_DISABLED] = ic.disabled; o[INFO_CUM_REWARD] = c.cum_reward_info;
   o[INFO_CUM_IMPACT] = c.cum_impact;
-  o[INFO_ON_TRACK] = query_on_wall(S, c.xf.p.x, c.xf.p.y, 0.5) ? 0.0 : 1.0;
+  o[INFO_ON_TRACK] = ic.on_track;
   o[INFO_RPM] = c.rpm; o[INFO_SIM_TIME] = P.env_time[env]; o[INFO_NCT] = c.nct; o[INFO_ERROR] = c.overflow;
   // CarEnv._calculate_track_progress of the current position (src/car_env.py:1544-1611): the reward pass
   // stores it every step for every car that is not disabled (and reset_car for the start pose)
@@ -2743,6 +2813,61 @@ __global__ void __launch_bounds__(SBLOCK) info_kernel(Params P, double* info) {
   } else {
     o[INFO_PERF_COUNT] = -1.0; o[INFO_PERF_MAX] = 0.0; o[INFO_PERF_FIRST] = -1.0;
   }
+}
+
+// On-device fitness accumulators (nascar_set_fitness): what learn/genetic_trainer.py:253-285 gathers per individual
+// from rewards[i] and info['cars'][i] after every step, in float64 as its Python floats.  acc is SoA [FIT_N][N] (a
+// wave's lanes touch contiguous lines); ended [E] is set after the step whose env flags carry terminated or
+// truncated -- that step is counted, then the env's cars stop accumulating (the trainer breaks out of its loop there).
+// lap_time: last_lap_time at the first step with lap_count > 0 (the trainer's own lines 280-283 leave it None for
+// ever; this is their evident intent).  disabled_at: the value of `steps` at the first step that left the car disabled
+// (0: never).  A block holds 256 / C whole envs, so the barrier orders every read of an env's ended byte before its
+// write.  Env slots [slot0, slot0 + nslot) of the block map (a shard's, or all).
+enum { FIT_REWARD, FIT_DISTANCE, FIT_MAX_SPEED, FIT_ON_TRACK, FIT_LAP_DONE, FIT_LAP_TIME, FIT_STEPS, FIT_DISABLED_AT, FIT_N };
+__global__ void __launch_bounds__(256) fitness_kernel(Params P, int slot0, int nslot, const float* reward,
+                                                      const uint8_t* env_flags, double* acc, uint8_t* ended) {
+  const int C = P.C, epw = 256 / C;
+  const int el = threadIdx.x / C, car = threadIdx.x - el * C, sl = blockIdx.x * epw + el;
+  int env = -1, b = 0;
+  if (el < epw && sl < nslot) {
+    b = (slot0 + sl) / P.epb;
+    if (!blk_empty(P, b)) env = blk_env_of(P, 0, slot0 + sl);
+  }
+  const bool live = env >= 0 && !ended[env];
+  if (live) {
+    const TrackDev T = P.tracks[blk_track_of(P, b)];
+    const WallSet S{T.walls, T.nwall, T.bp, T.sn, T.wfat};
+    const int n = env * C + car;
+    const size_t N = (size_t)P.N;
+    Car c;
+    car_load(P, n, c);
+    const InfoCore ic = info_core(S, c);
+    acc[FIT_REWARD * N + n] += (double)reward[n];
+    const double mx = acc[FIT_MAX_SPEED * N + n];
+    acc[FIT_MAX_SPEED * N + n] = ic.speed > mx ? ic.speed : mx;        // max(max_speed, speed)
+    acc[FIT_DISTANCE * N + n] += ic.speed * (1.0 / 60.0);
+    if (ic.on_track != 0.0) acc[FIT_ON_TRACK * N + n] += 1.0 / 60.0;
+    if (ic.laps > 0 && acc[FIT_LAP_DONE * N + n] == 0.0) {
+      acc[FIT_LAP_DONE * N + n] = 1.0;
+      acc[FIT_LAP_TIME * N + n] = ic.last_lap;
+    }
+    const double steps = acc[FIT_STEPS * N + n] + 1.0;
+    acc[FIT_STEPS * N + n] = steps;
+    if (ic.disabled && acc[FIT_DISABLED_AT * N + n] == 0.0) acc[FIT_DISABLED_AT * N + n] = steps;
+  }
+  __syncthreads();
+  if (live && car == 0 && (env_flags[env] & (EF_TERMINATED | EF_TRUNCATED))) ended[env] = 1;
+}
+// nascar_get_fitness: the accumulators as [N][FIT_N] rows; lap_time NaN until a lap is completed, disabled_at_step -1
+// for a car that was never disabled
+__global__ void __launch_bounds__(256) fitness_read_kernel(int N, const double* acc, double* out) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  double v[FIT_N];
+  for (int f = 0; f < FIT_N; ++f) v[f] = acc[(size_t)f * N + n];
+  if (v[FIT_LAP_DONE] == 0.0) v[FIT_LAP_TIME] = NAN;
+  if (v[FIT_DISABLED_AT] == 0.0) v[FIT_DISABLED_AT] = -1.0;
+  for (int f = 0; f < FIT_N; ++f) out[(size_t)n * FIT_N + f] = v[f];
 }
 
 // ------------------------------------------------------------------ random-track mode (CarEnv(track_file=None))
@@ -3400,6 +3525,13 @@ struct NascarHandle {
   MlpDev* d_ctrl = nullptr;
   bool field_set = false;
   int field[MLP_MAX_CARS];
+  // genome drivers (policy 5, NASCAR_CTRL_GENOME): the per-car gene records, outside the state arena; their upload is
+  // staged in pinned memory and ordered on the caller's stream (ev_genome: the staging buffer is free again)
+  GenomeRec* d_genome = nullptr; bool genome_set = false;
+  GenomeRec* h_genome = nullptr; hipEvent_t ev_genome = nullptr;
+  // on-device fitness (nascar_set_fitness): one allocation -- acc [FIT_N][N] float64, ended [E], env flags [E] of the
+  // steps whose caller passed none
+  double* d_fit = nullptr; uint8_t* d_fit_ended = nullptr; uint8_t* d_fit_flags = nullptr; bool fit_on = false;
   size_t max_lds = 0, max_sensor_lds = 0, max_sensor_groups_lds = 0;
   bool dirty_tracks = true;
   // sharded rollout (nascar_set_rollout_streams): shard s steps workgroups [nblocks*s/S, nblocks*(s+1)/S) on its
@@ -3566,6 +3698,10 @@ extern "C" void nascar_destroy(NascarHandle* h) {
   for (void* p : h->ctrl_mem) hipFree(p);
   hipFree(h->d_ctrl);
   hipFree(h->d_rt);
+  if (h->ev_genome) { hipEventSynchronize(h->ev_genome); hipEventDestroy(h->ev_genome); }
+  if (h->h_genome) hipHostFree(h->h_genome);
+  hipFree(h->d_genome);
+  hipFree(h->d_fit);
   delete h;
 }
 
@@ -4264,13 +4400,51 @@ extern "C" int nascar_set_step_events(NascarHandle* h, void* const* events, int3
   return 0;
 }
 
+// fitness accumulation (nascar_set_fitness) of one step for the cars of workgroups [b0, b1), after their sensor launch
+static int launch_fitness(NascarHandle* h, const Params& P, int b0, int b1, const float* reward, const uint8_t* env_flags,
+                          hipStream_t s) {
+  const int nslot = (b1 - b0) * h->epb, epw = 256 / h->C;
+  if (nslot <= 0) return 0;
+  hipLaunchKernelGGL(fitness_kernel, dim3((nslot + epw - 1) / epw), dim3(256), 0, s, P, b0 * h->epb, nslot, reward, env_flags,
+                     h->d_fit, h->d_fit_ended);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// The accumulators take an env's terminal step and freeze; an auto-reset would put the reset state under that step's
+// speed and on_track, so the two are refused together (evaluation steps past termination, as the trainer's env does)
+static int fitness_refused(const NascarHandle* h, int auto_reset) {
+  if (h->fit_on && auto_reset)
+    return fail("fitness accumulation (nascar_set_fitness) needs auto_reset = 0: the accumulators read each env's "
+                "state after its terminal step");
+  if (h->fit_on && h->rt_on) return fail("fitness accumulation (nascar_set_fitness) is not available in random-track mode");
+  return 0;
+}
+// the genome driver's launch for a shard's workgroups [b0, b1) (b0 < 0: the cars [n0, n1) directly)
+static int launch_genome(NascarHandle* h, const Params& P, int b0, int b1, int n0, int n1, uint64_t slots, const float* obs,
+                         float* act, hipStream_t s) {
+  const int nslot = b0 < 0 ? 0 : (b1 - b0) * h->epb;
+  const int lanes = b0 < 0 ? n1 - n0 : nslot * h->C;
+  if (lanes <= 0) return 0;
+  hipLaunchKernelGGL(genome_policy_kernel, dim3((lanes + 255) / 256), dim3(256), 0, s, P, b0 < 0 ? -1 : b0 * h->epb, nslot,
+                     n0, n1, slots, obs, act, h->d_ctl, h->d_genome);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 static int step_impl(NascarHandle* h, const void* actions, int32_t discrete, int policy, uint64_t seed, int64_t step,
                      float* obs, float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset,
                      float* terminal_obs, void* stream) {
-  if (vis_refused(h)) return -1;
+  if (vis_refused(h) || fitness_refused(h, auto_reset)) return -1;
   h->pristine = false;
   if (prepare(h, (hipStream_t)stream)) return -1;
   Params P = make_params(h);
+  if (h->fit_on) {
+    uint8_t* ef = env_flags ? env_flags : h->d_fit_flags;
+    if (launch_step_range(h, P, h->nblocks, actions, discrete, policy, seed, step, obs, obs, reward, car_flags, ef, 0,
+                          terminal_obs, (hipStream_t)stream))
+      return -1;
+    return launch_fitness(h, P, 0, h->nblocks, reward, ef, (hipStream_t)stream);
+  }
   // Whole grid on the caller's stream: splitting one step over streams needs a fork and a join per step, and
   // the per-step barrier measured slower than one grid (tools/streams_exp.py: 2 / 4 shards 0.252 / 0.277 ms vs
   // 0.224 ms).  Shards pay off only when they run many steps unsynchronised: the sharded nascar_rollout.
@@ -4293,6 +4467,9 @@ extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed
   if (policy == 2 || policy == 4)
     return fail("driven step: policy %d (MLP controllers) runs in launches of its own -- use nascar_policy_actions + nascar_step "
                 "or nascar_rollout", policy);
+  if (policy == 5)
+    return fail("driven step: policy 5 (genome drivers) runs in a launch of its own -- use nascar_policy_actions + nascar_step "
+                "or nascar_rollout");
   if (policy != 0 && policy != 1 && policy != 3) return fail("driven step policy must be 0, 1 or 3 (got %d)", policy);
   return step_impl(h, nullptr, 0, policy, seed, step, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
 }
@@ -4318,13 +4495,14 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
   S = std::max(1, std::min(S, h->nblocks));
   const bool rt = h->rt_on && auto_reset;
   if (h->rt_on) S = 1;   // random-track mode: the block map changes between steps, so no shard owns a fixed set of envs
-  const bool field = policy == 4;
-  const bool actor = policy == 2 || field;   // the actions come from a launch of their own, into d_ro_act
+  const bool field = policy == 4, genome = policy == 5;
+  const bool actor = policy == 2 || field || genome;   // the actions come from a launch of their own, into d_ro_act
   if (actor) {
     if (field && !h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
-    if (!field && !h->d_actor) return fail("policy 2 needs an actor (nascar_set_actor)");
-    if (!field && ((uintptr_t)obs & 7)) return fail("actor obs must be 8-byte aligned");
-    if (!h->map_identity) S = 1;
+    if (genome && !h->genome_set) return fail("policy 5 needs a genome table (nascar_set_genomes)");
+    if (policy == 2 && !h->d_actor) return fail("policy 2 needs an actor (nascar_set_actor)");
+    if (policy == 2 && ((uintptr_t)obs & 7)) return fail("actor obs must be 8-byte aligned");
+    if (!h->map_identity && !genome) S = 1;   // the genome driver walks its shard's env slots of the block map
     if (!h->d_ro_act) HIPCHK(hipMalloc(&h->d_ro_act, sizeof(float) * 2 * (size_t)h->N));
   }
   if ((int)h->sub_stream.size() < S - 1 || (S > 1 && !h->ev_fork)) {   // on the handle's device, whatever is current
@@ -4366,7 +4544,9 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
           if (actor && ph == 0) {
             const size_t c0 = S == 1 ? 0 : (size_t)b0 * h->epb * h->C;
             const size_t c1 = S == 1 ? NC : std::min((size_t)b1 * h->epb, E) * h->C;
-            if (field) {
+            if (genome) {
+              if (launch_genome(h, P, b0, b1, 0, 0, ~0ull, o_in, h->d_ro_act, shard_stream(s))) return -1;
+            } else if (field) {
               if (launch_field(h, (int)(c0 / h->C), (int)((c1 - c0) / h->C), seed, step0 + k, o_in, h->d_ro_act, shard_stream(s)))
                 return -1;
             } else if (c1 > c0) launch_actor(h, (int)(c1 - c0), o_in + c0 * 38, h->d_ro_act + c0 * 2, shard_stream(s));
@@ -4375,8 +4555,11 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
           if (launch_step_range(h, P, b1 - b0, actor ? h->d_ro_act : nullptr, 0, actor ? -1 : policy, seed, step0 + k,
                                 o_in, o_out, reward + ko * NC,
                                 car_flags ? car_flags + ko * NC : nullptr,
-                                env_flags ? env_flags + ko * E : (rt ? h->d_rt_flags : nullptr),
+                                env_flags ? env_flags + ko * E : (rt ? h->d_rt_flags : h->fit_on ? h->d_fit_flags : nullptr),
                                 auto_reset, nullptr, shard_stream(s), 1 << ph, ph == 1))
+            return -1;
+          if (h->fit_on && ph == 2 &&
+              launch_fitness(h, P, b0, b1, reward + ko * NC, env_flags ? env_flags + ko * E : h->d_fit_flags, shard_stream(s)))
             return -1;
         }
       }
@@ -4504,11 +4687,19 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
                               float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, int32_t traj,
                               void* stream) {
   if (!h || !obs || !reward) return fail("null argument");
-  if (policy < 0 || policy > 4) return fail("rollout policy must be 0, 1, 2, 3 or 4 (got %d)", policy);
+  if (policy < 0 || policy > 5) return fail("rollout policy must be 0, 1, 2, 3, 4 or 5 (got %d)", policy);
   if (policy == 2 && h->ro_streams == 0) return fail("the fused rollout kernel has no actor (policy 2): use the sharded rollout");
   if (policy == 4 && h->ro_streams == 0)
     return fail("the fused rollout kernel has no controllers (policy 4): use the sharded rollout (rollout streams >= 1)");
   if (policy == 4 && !h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
+  if (policy == 5 && !h->genome_set) return fail("policy 5 needs a genome table (nascar_set_genomes)");
+  if (policy == 5 && h->ro_streams == 0)
+    return fail("the fused rollout kernel has no genome drivers (policy 5): use the sharded rollout (rollout streams >= 1)");
+  if (policy == 5 && h->ro_pipe > 0)
+    return fail("the pipelined rollout has no genome drivers (policy 5): switch it off (nascar_set_rollout_pipe(h, 0))");
+  if (h->fit_on && (h->ro_streams == 0 || h->ro_pipe > 0))
+    return fail("fitness accumulation (nascar_set_fitness) runs on the sharded rollout only (rollout streams >= 1, no pipe)");
+  if (fitness_refused(h, auto_reset)) return -1;
   if (h->rt_on && h->ro_streams == 0)
     return fail("random-track mode needs the sharded rollout (rollout streams >= 1): the fused kernel keeps one block map");
   if (traj & ~(NASCAR_TRAJ_RECORDS | NASCAR_TRAJ_OBS)) return fail("unknown trajectory flags 0x%x", traj);
@@ -4682,11 +4873,68 @@ extern "C" int nascar_set_state(NascarHandle* h, const void* src, void* stream) 
   return 0;
 }
 
+// ------------------------------------------------------------------ genome drivers and on-device fitness
+extern "C" int nascar_set_genomes(NascarHandle* h, const double* genomes, void* stream) {
+  if (!h) return fail("null argument");
+  if (!genomes) { h->genome_set = false; return 0; }
+  const size_t N = (size_t)h->N;
+  for (size_t i = 0; i < N * 12; ++i)
+    if (!std::isfinite(genomes[i]))
+      return fail("genome of car %zu: gene %zu is not finite (%g)", i / 12, i % 12, genomes[i]);
+  int cur = 0;
+  HIPCHK(hipGetDevice(&cur));
+  if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
+  hipError_t e = hipSuccess;
+  if (!h->d_genome) e = hipMalloc(&h->d_genome, sizeof(GenomeRec) * N);
+  if (e == hipSuccess && !h->h_genome) e = hipHostMalloc((void**)&h->h_genome, sizeof(GenomeRec) * N);
+  if (e == hipSuccess && !h->ev_genome) e = hipEventCreateWithFlags(&h->ev_genome, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventSynchronize(h->ev_genome);   // the previous upload has left the staging buffer
+  if (e == hipSuccess) {
+    for (size_t n = 0; n < N; ++n) {
+      GenomeRec& r = h->h_genome[n];
+      memcpy(r.g, genomes + 12 * n, sizeof r.g);
+      r.py_steer = 0; r.pad = 0;
+    }
+    e = hipMemcpyAsync(h->d_genome, h->h_genome, sizeof(GenomeRec) * N, hipMemcpyHostToDevice, (hipStream_t)stream);
+  }
+  if (e == hipSuccess) e = hipEventRecord(h->ev_genome, (hipStream_t)stream);
+  // a new table is a new set of controllers: GeneticController.__init__ starts each from a zero control_state
+  if (e == hipSuccess) e = hipMemsetAsync(h->d_ctl, 0, sizeof(double) * 4 * N, (hipStream_t)stream);
+  if (cur != h->cfg.device) hipSetDevice(cur);
+  if (e != hipSuccess) return fail("uploading the genome table failed: %s", hipGetErrorString(e));
+  h->genome_set = true;
+  return 0;
+}
+extern "C" int nascar_set_fitness(NascarHandle* h, int32_t enable, void* stream) {
+  if (!h) return fail("null argument");
+  if (!enable) { h->fit_on = false; return 0; }
+  const size_t acc_bytes = align256(sizeof(double) * FIT_N * (size_t)h->N), e_bytes = align256((size_t)h->E);
+  if (!h->d_fit) {
+    HIPCHK(hipMalloc(&h->d_fit, acc_bytes + 2 * e_bytes));
+    h->d_fit_ended = (uint8_t*)h->d_fit + acc_bytes;
+    h->d_fit_flags = h->d_fit_ended + e_bytes;
+  }
+  HIPCHK(hipMemsetAsync(h->d_fit, 0, acc_bytes + 2 * e_bytes, (hipStream_t)stream));
+  h->fit_on = true;
+  return 0;
+}
+extern "C" int nascar_get_fitness(NascarHandle* h, double* out, void* stream) {
+  if (!h || !out) return fail("null argument");
+  if (!h->d_fit) return fail("no fitness accumulators: enable them first (nascar_set_fitness)");
+  hipLaunchKernelGGL(fitness_read_kernel, dim3((h->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->N, h->d_fit, out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, const float* obs,
                                      float* actions, void* stream) {
   if (!h || !actions) return fail("null argument");
-  if (policy < 0 || policy > 4) return fail("unknown policy %d", policy);
+  if (policy < 0 || policy > 5) return fail("unknown policy %d", policy);
   if (policy >= 1 && !obs) return fail("policy %d needs obs", policy);
+  if (policy == 5) {
+    if (!h->genome_set) return fail("policy 5 needs a genome table (nascar_set_genomes)");
+    return launch_genome(h, make_params(h), -1, 0, 0, h->N, ~0ull, obs, actions, (hipStream_t)stream);
+  }
   if (policy == 4) {
     if (!h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
     if ((uintptr_t)actions & 7) return fail("field actions must be 8-byte aligned");
@@ -4955,9 +5203,10 @@ extern "C" int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl) 
   if (!h) return fail("null argument");
   if (!ctrl) { h->field_set = false; return 0; }
   for (int c = 0; c < h->C; ++c)
-    if (ctrl[c] < NASCAR_CTRL_NOISY || ctrl[c] >= (int)h->ctrl.size())
+    if (ctrl[c] < NASCAR_CTRL_GENOME || (ctrl[c] == NASCAR_CTRL_GENOME && !h->genome_set) || ctrl[c] >= (int)h->ctrl.size())
       return fail("car slot %d: unknown controller id %d (%d loaded with nascar_add_controller; built-in sources are -1 rule, "
-                  "-2 uniform, -3 noisy rule)", c, ctrl[c], (int)h->ctrl.size());
+                  "-2 uniform, -3 noisy rule, and -4 the genome driver once a genome table is set with nascar_set_genomes)",
+                  c, ctrl[c], (int)h->ctrl.size());
   for (int c = 0; c < h->C; ++c) h->field[c] = ctrl[c];
   h->field_set = true;
   return 0;
@@ -4984,7 +5233,9 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
   const int gx = ((nenv + 31) / 32 + AM_WAVES - 1) / AM_WAVES;
   bool done[MLP_MAX_CARS] = {};
   bool builtin = false;
+  uint64_t genome_slots = 0;   // slots of NASCAR_CTRL_GENOME: genome_policy_kernel, as policy 5 runs it for those cars
   for (int c = 0; c < C; ++c) {
+    if (h->field[c] == NASCAR_CTRL_GENOME) { genome_slots |= 1ull << c; continue; }
     if (h->field[c] < 0) { builtin = true; continue; }
     if (done[c]) continue;
     const MlpDev& K = h->ctrl[h->field[c]];
@@ -5002,10 +5253,14 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
       return fail("no kernel for controller shape %d-%d", K.h1, K.h2);
     HIPCHK(hipGetLastError());
   }
+  const int n0 = env0 * C, n1 = (env0 + nenv) * C;
+  if (genome_slots) {
+    if (!h->genome_set) return fail("a genome slot of the field needs a genome table (nascar_set_genomes)");
+    if (launch_genome(h, make_params(h), -1, 0, n0, n1, genome_slots, obs, act, s)) return -1;
+  }
   if (builtin) {
     FieldCodes F{};
-    for (int c = 0; c < C; ++c) F.code[c] = (signed char)std::max(h->field[c], -4);
-    const int n0 = env0 * C, n1 = (env0 + nenv) * C;
+    for (int c = 0; c < C; ++c) F.code[c] = (signed char)std::max(h->field[c], NASCAR_CTRL_GENOME);   // the lowest code
     hipLaunchKernelGGL(field_policy_kernel, dim3((n1 - n0 + 255) / 256), dim3(256), 0, s, n0, n1, C, F, seed, step, obs, act,
                        h->d_ctl);
     HIPCHK(hipGetLastError());
