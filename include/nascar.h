@@ -227,8 +227,17 @@ int nascar_get_info(NascarHandle* h, double* info, void* stream);
  * terms in the normal / tangent masses; fixture mixing of two car fixtures (friction sqrt(0.7 * 0.7), restitution
  * max(0.1, 0.1) as a velocity bias below -1 m/s), applied to both cars' linear and angular velocity.  Solved after (not
  * interleaved with) each car's wall island, point by point (no 2-point block solver), without warm start or position
- * correction.  The normal impulses count in the cars' collision impulse (damage / impact disables).  Default 0
- * (reference behaviour); parity runs with 0.  Takes effect from the next reset (start grid) and step. */
+ * correction.  The relative velocity at a contact point is formed in b2ContactSolver's association,
+ * vB + wB x rB - vA - wA x rA, left to right.  The normal impulses count in the cars' collision impulse (damage / impact
+ * disables).  WRITE-BACK: every car that a solved pair holds takes the solved velocity (the last normal pass can bring a
+ * pair's normal impulse back to 0 after its friction, clamped by the iteration before, has moved both cars); a car whose
+ * largest accumulated normal impulse is > 0 is also woken and reports the impulse (car flag bit 2); every other car keeps
+ * the velocity its own Box2D step gave it.
+ * CAPACITY: an env keeps at most num_cars touching pairs per step, taken in (i, j) order, i < j (num_cars * (num_cars -
+ * 1) / 2 can touch in a pile of >= 4 cars, since overlap is not corrected).  Further touching pairs are not solved that
+ * step; both cars of such a pair get the error flag (car flag bit 7, info's `error`), as after a wall-contact overflow,
+ * until the env is reset.
+ * Default 0 (reference behaviour); parity runs with 0.  Takes effect from the next reset (start grid) and step. */
 int nascar_set_car_contact(NascarHandle* h, int32_t enable);
 
 /* BUILD-ONLY EXTENSION, no reference counterpart (the reference's ray-cast callback drops every fixture that is not a
@@ -397,6 +406,16 @@ int nascar_debug_f64math(const double* x, const double* y, double* out, int32_t 
  *   x y, point 0 x y id, point 1 x y id, 0. */
 int nascar_debug_toi(const float* cases, int32_t n, float* beta, int32_t* state, int32_t* far, void* stream);
 int nascar_debug_collide(const float* cases, int32_t n, float* out, void* stream);
+
+/* Test hook: the car-car contact solver of nascar_set_car_contact alone, on caller-given bodies (device pointers, no
+ * engine state), in the step's lane layout: lane el * num_cars + car, 128 / num_cars envs per 128-lane workgroup, the
+ * env's car-0 lane solving it with the step's own function.  bodies [num_envs * num_cars][7] float32: x y qs qc vx vy w
+ * (body centre, the rotation's sine and cosine, linear and angular velocity).  out [num_envs * num_cars][4] float32:
+ * vx vy w after the solve and the car's largest accumulated normal impulse, before the step's write-back rule (above).
+ * env_out [num_envs][2] int32: touching pairs solved, touching pairs dropped at the cap of num_cars.
+ * num_cars in [1, 64]; with 1 car nothing is solved. */
+int nascar_debug_car_contact(const float* bodies, int32_t num_envs, int32_t num_cars, float* out, int32_t* env_out,
+                             void* stream);
 
 /* Test hook: sensors only.  poses: device float32 [E*C*3] (x, y, angle) per car, written into the sensor
  * hand-off; impl 1 = beam-list ray kernel (the step's default), 0 = wall-group kernel; writes the 16

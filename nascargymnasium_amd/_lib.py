@@ -167,6 +167,8 @@ def lib():
     L.nascar_debug_toi.restype = ctypes.c_int
     L.nascar_debug_collide.argtypes = [vp, i32, vp, vp]
     L.nascar_debug_collide.restype = ctypes.c_int
+    L.nascar_debug_car_contact.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.nascar_debug_car_contact.restype = ctypes.c_int
     L.nascar_debug_sensors.argtypes = [vp, vp, vp, i32, vp]
     L.nascar_debug_sensors.restype = ctypes.c_int
     i32p, u64p = ctypes.POINTER(i32), ctypes.POINTER(u64)
@@ -198,7 +200,7 @@ EXPORTED = ["nascar_create", "nascar_destroy", "nascar_last_error", "nascar_add_
             "nascar_set_state", "nascar_policy_actions", "nascar_set_step_events", "nascar_set_actor", "nascar_set_actor_precision", "nascar_actor_forward",
             "nascar_check_controller", "nascar_add_controller", "nascar_controller_forward", "nascar_set_car_controllers",
             "nascar_set_genomes", "nascar_set_fitness", "nascar_get_fitness",
-            "nascar_debug_sincosf", "nascar_debug_f64math", "nascar_debug_toi", "nascar_debug_collide", "nascar_debug_sensors", "nascar_track_draw", "nascar_set_random_tracks",
+            "nascar_debug_sincosf", "nascar_debug_f64math", "nascar_debug_toi", "nascar_debug_collide", "nascar_debug_car_contact", "nascar_debug_sensors", "nascar_track_draw", "nascar_set_random_tracks",
             "nascar_get_env_tracks", "nascar_vec_post", "nascar_check_actions", "nascar_set_track_cache",
             "nascar_prebuild_track", "nascar_debug_block_map"]
 

@@ -254,6 +254,22 @@ class BatchedCarEnv:
         epb = self.envs_per_block
         return bt[:nb].cpu().numpy(), be[:nb * epb].cpu().numpy().reshape(nb, epb)
 
+    @staticmethod
+    def debug_car_contact(bodies: torch.Tensor, num_cars: int):
+        """nascar_debug_car_contact (test hook, no engine state): the car-car contact solver on bodies [E * num_cars, 7]
+        float32 on the device (x y qs qc vx vy w).  Returns (out [E, num_cars, 4] float32: vx vy w and the car's largest
+        normal impulse, env_out [E, 2] int32: pairs solved, pairs dropped at the cap) as device tensors."""
+        b = bodies.to(torch.float32).contiguous().reshape(-1, 7)
+        C = int(num_cars)
+        if C < 1 or b.shape[0] % C:
+            raise ValueError(f"{b.shape[0]} bodies are no whole envs of {C} cars")
+        E = b.shape[0] // C
+        out = torch.zeros(E, C, 4, dtype=torch.float32, device=b.device)
+        env_out = torch.zeros(E, 2, dtype=torch.int32, device=b.device)
+        with torch.cuda.device(b.device):
+            _lib.check(_lib.lib().nascar_debug_car_contact(_ptr(b), E, C, _ptr(out), _ptr(env_out), _stream()))
+        return out, env_out
+
     # ------------------------------------------------------------------ core API
     def reset(self, env_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """CarEnv.reset for all envs (or those with env_mask[e] != 0, uint8[E] on device)."""

@@ -2233,20 +2233,35 @@ __device__ __forceinline__ void logic_run(const Params& P, const TrackDev& T, co
 // does not: the car-car constraints are solved after (not interleaved with) each car's wall island, with no warm start
 // across steps, the 2-point block solver replaced by point-by-point sequential impulses, and no position correction (the
 // per-car Box2D steps, their proxies and TOI sweeps are done; overlap is removed by the velocities over the next steps).
+// The relative velocity at a contact point is b2ContactSolver's expression in its association, vB + wB x rB - vA -
+// wA x rA (cc_rel_vel), in the set-up and in both loops: tests/test_gpu_car_contact.py compares the solve bit for bit
+// with the oracle's restatement of Box2D for two dynamic bodies (or_car_contact).
+// Capacity: an env's C LDS slots hold at most C touching pairs, taken in (i, j) order; a pile of >= 4 cars can have
+// more (up to C (C - 1) / 2: overlap is not corrected).  A pair past the cap goes unsolved that step and raises both
+// cars' `overflow` field (CF_ERROR, info's error) until the env is reset, like a wall-contact overflow.
+// Write-back: every car a solved contact holds takes the solved velocity; a car whose largest accumulated normal
+// impulse is > 0 is also woken and has the impulse counted (car flag bit 2).
 // One lane per env (its car 0) solves the env; the bodies and constraints sit in the caller's LDS scratch
 // (CC_LDS_BYTES).  Sensors still see walls only.  Default off; every parity test runs with it off.
 #define CAR_FRICTION_MIX 0.7f      // sqrt(CAR_FRICTION * CAR_FRICTION)
 #define CAR_RESTITUTION_MIX 0.1f   // max(CAR_RESTITUTION, CAR_RESTITUTION)
 #define CC_VELOCITY_ITERATIONS 6   // BOX2D_VELOCITY_ITERATIONS (src/constants/physics.py:16)
-struct CCBody { V2 c; Rot q; V2 v; float w, jmax; };
+#define CC_TOUCHED 1               // CCBody::mark: a solved contact holds this car
+#define CC_DROPPED 2               // CCBody::mark: a touching pair of this car was dropped at the cap
+struct CCBody { V2 c; Rot q; V2 v; float w, jmax; int mark; };
 struct CCon {                       // one touching car pair: b2ContactVelocityConstraint for two dynamic bodies
   int ia, ib, np; V2 n;
   V2 rA[2], rB[2]; float nm[2], tm[2], vb[2], ni[2], ti[2];
 };
 #define CC_LDS_BYTES ((size_t)SBLOCK * (sizeof(CCBody) + sizeof(CCon)))
-__device__ __attribute__((noinline)) void car_contact_env(CCBody* B, CCon* K, int C, int kcap) {
+struct CCStat { int solved, dropped; };   // an env's touching pairs: solved, and dropped at the cap
+// b2ContactSolver's relative velocity at a contact point, in its association: vB + wB x rB - vA - wA x rA
+__device__ __forceinline__ V2 cc_rel_vel(V2 vA, float wA, V2 vB, float wB, V2 rA, V2 rB) {
+  return vsub(vsub(vadd(vB, vcross_sv(wB, rB)), vA), vcross_sv(wA, rA));
+}
+__device__ __attribute__((noinline)) CCStat car_contact_env(CCBody* B, CCon* K, int C, int kcap) {
   Poly box; make_box(&box, CAR_HX, CAR_HY);
-  int nk = 0;
+  int nk = 0, ndrop = 0;
   for (int i = 0; i < C; ++i)
     for (int j = i + 1; j < C; ++j) {
       const CCBody A = B[i], D = B[j];
@@ -2255,7 +2270,12 @@ __device__ __attribute__((noinline)) void car_contact_env(CCBody* B, CCon* K, in
       Xf xb; xb.p = D.c; xb.q = D.q;
       DContact m;
       collide_polygons(m, &box, xa, &box, xb);
-      if (m.pointCount == 0 || nk == kcap) continue;
+      if (m.pointCount == 0) continue;
+      if (nk == kcap) {   // the env's slots are full: the pair goes unsolved and both cars carry the error flag
+        B[i].mark |= CC_DROPPED; B[j].mark |= CC_DROPPED; ++ndrop;
+        continue;
+      }
+      B[i].mark |= CC_TOUCHED; B[j].mark |= CC_TOUCHED;
       V2 nrm, pts[2];
       world_manifold(m, xa, xb, &nrm, pts);
       CCon k;
@@ -2273,13 +2293,14 @@ __device__ __attribute__((noinline)) void car_contact_env(CCBody* B, CCon* K, in
         const float rtA = vcross(rA, t), rtB = vcross(rB, t);
         const float kt = CAR_INV_MASS + CAR_INV_MASS + CAR_INV_I * rtA * rtA + CAR_INV_I * rtB * rtB;
         k.tm[q] = kt > 0.0f ? fdiv_cr(1.0f, kt) : 0.0f;
-        const V2 dv = vsub(vadd(D.v, vcross_sv(D.w, rB)), vadd(A.v, vcross_sv(A.w, rA)));
+        const V2 dv = cc_rel_vel(A.v, A.w, D.v, D.w, rA, rB);
         const float vrel = vdot(nrm, dv);
         if (vrel < -VELOCITY_THRESHOLD) k.vb[q] = -CAR_RESTITUTION_MIX * vrel;
       }
       K[nk++] = k;
     }
-  if (nk == 0) return;
+  const CCStat st = {nk, ndrop};
+  if (nk == 0) return st;
   for (int it = 0; it < CC_VELOCITY_ITERATIONS; ++it)
     for (int kk = 0; kk < nk; ++kk) {
       CCon& k = K[kk];
@@ -2288,7 +2309,7 @@ __device__ __attribute__((noinline)) void car_contact_env(CCBody* B, CCon* K, in
       V2 vA = A.v, vB = D.v; float wA = A.w, wB = D.w;
       const V2 nrm = k.n, t = vcross_vs(nrm, 1.0f);
       for (int q = 0; q < k.np; ++q) {   // friction first, as b2ContactSolver::SolveVelocityConstraints
-        const V2 dv = vsub(vadd(vB, vcross_sv(wB, k.rB[q])), vadd(vA, vcross_sv(wA, k.rA[q])));
+        const V2 dv = cc_rel_vel(vA, wA, vB, wB, k.rA[q], k.rB[q]);
         const float vt = vdot(dv, t);
         float lambda = k.tm[q] * (-vt);
         const float maxF = CAR_FRICTION_MIX * k.ni[q];
@@ -2300,7 +2321,7 @@ __device__ __attribute__((noinline)) void car_contact_env(CCBody* B, CCon* K, in
         vB = vadd(vB, vmul(CAR_INV_MASS, Pt)); wB += CAR_INV_I * vcross(k.rB[q], Pt);
       }
       for (int q = 0; q < k.np; ++q) {   // normal: accumulated impulse clamped at >= 0
-        const V2 dv = vsub(vadd(vB, vcross_sv(wB, k.rB[q])), vadd(vA, vcross_sv(wA, k.rA[q])));
+        const V2 dv = cc_rel_vel(vA, wA, vB, wB, k.rA[q], k.rB[q]);
         const float vn = vdot(dv, nrm);
         float lambda = -k.nm[q] * (vn - k.vb[q]);
         const float ni = fmaxb(k.ni[q] + lambda, 0.0f);
@@ -2319,6 +2340,7 @@ __device__ __attribute__((noinline)) void car_contact_env(CCBody* B, CCon* K, in
     B[k.ia].jmax = fmaxb(B[k.ia].jmax, j);
     B[k.ib].jmax = fmaxb(B[k.ib].jmax, j);
   }
+  return st;
 }
 // every thread of the block calls it (block barriers); scratch: CC_LDS_BYTES of LDS
 __device__ __forceinline__ void car_contact_block(const Params& P, int tid, int el, int car, int env, int n,
@@ -2331,7 +2353,7 @@ __device__ __forceinline__ void car_contact_block(const Params& P, int tid, int 
     b.c = V(F32P(P, xpx)[n], F32P(P, xpy)[n]);      // (the body origin is its centre of mass)
     b.q.s = F32P(P, qs)[n]; b.q.c = F32P(P, qc)[n];
     b.v = V(F32P(P, vx)[n], F32P(P, vy)[n]); b.w = F32P(P, w)[n];
-    b.jmax = 0.0f;
+    b.jmax = 0.0f; b.mark = 0;
     B[tid] = b;
   }
   __syncthreads();
@@ -2339,12 +2361,45 @@ __device__ __forceinline__ void car_contact_block(const Params& P, int tid, int 
   __syncthreads();
   if (env >= 0) {
     const CCBody b = B[tid];
-    if (b.jmax > 0.0f) {
-      F32P(P, vx)[n] = b.v.x; F32P(P, vy)[n] = b.v.y; F32P(P, w)[n] = b.w;
+    // every car a solved contact holds takes the solved velocity: its last normal pass can bring a contact's normal
+    // impulse back to 0 after friction (clamped by the iteration before) has moved both cars, and its partner is stored
+    if (b.mark & CC_TOUCHED) { F32P(P, vx)[n] = b.v.x; F32P(P, vy)[n] = b.v.y; F32P(P, w)[n] = b.w; }
+    if (b.jmax > 0.0f) {   // PostSolve reports an impulse: woken, counted in the collision impulse (car flag bit 2)
       if (!I32P(P, awake)[n]) { I32P(P, awake)[n] = 1; F32P(P, sleep)[n] = 0.0f; }
       if (!I32P(P, imp_present)[n]) { I32P(P, imp_present)[n] = 1; F64P(P, imp)[n] = 0.0; }
       F64P(P, imp)[n] = pymax(F64P(P, imp)[n], (double)b.jmax);
     }
+    if (b.mark & CC_DROPPED) I32P(P, overflow)[n] = 1;   // CF_ERROR / info's error, until the env is reset
+  }
+}
+// nascar_debug_car_contact: car_contact_env on caller-given bodies, in the step's lane layout (lane el * C + car,
+// SBLOCK / C envs per workgroup, the env's car-0 lane solves it); out is the LDS state before any write-back gate
+__global__ void __launch_bounds__(SBLOCK) debug_car_contact_kernel(const float* bodies, int E, int C, float* out,
+                                                                   int32_t* env_out) {
+  const int tid = threadIdx.x, epb = SBLOCK / C;
+  const int el = tid / C, car = tid - el * C;
+  const int slot = blockIdx.x * epb + el;
+  const int env = el < epb && slot < E ? slot : -1;
+  const size_t n = env >= 0 ? (size_t)env * C + car : 0;
+  CCBody* B = (CCBody*)smem;
+  CCon* K = (CCon*)(smem + (size_t)SBLOCK * sizeof(CCBody));
+  if (env >= 0) {
+    const float* k = bodies + n * 7;
+    CCBody b;
+    b.c = V(k[0], k[1]); b.q.s = k[2]; b.q.c = k[3];
+    b.v = V(k[4], k[5]); b.w = k[6];
+    b.jmax = 0.0f; b.mark = 0;
+    B[tid] = b;
+  }
+  __syncthreads();
+  CCStat st = {0, 0};
+  if (env >= 0 && car == 0 && C > 1) st = car_contact_env(B + tid, K + tid, C, C);
+  __syncthreads();
+  if (env >= 0) {
+    const CCBody b = B[tid];
+    float* o = out + n * 4;
+    o[0] = b.v.x; o[1] = b.v.y; o[2] = b.w; o[3] = b.jmax;
+    if (car == 0) { env_out[(size_t)env * 2] = st.solved; env_out[(size_t)env * 2 + 1] = st.dropped; }
   }
 }
 __global__ void __launch_bounds__(SBLOCK) car_contact_kernel(Params P) {
@@ -5309,6 +5364,17 @@ extern "C" int nascar_debug_collide(const float* cases, int32_t n, float* out, v
   if (!cases || !out || n < 0) return fail("bad argument");
   if (n == 0) return 0;
   hipLaunchKernelGGL(debug_collide_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, cases, n, out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+extern "C" int nascar_debug_car_contact(const float* bodies, int32_t num_envs, int32_t num_cars, float* out,
+                                        int32_t* env_out, void* stream) {
+  if (!bodies || !out || !env_out || num_envs < 0) return fail("bad argument");
+  if (num_cars < 1 || num_cars > 64) return fail("num_cars must be in [1, 64]");
+  if (num_envs == 0) return 0;
+  const int epb = SBLOCK / num_cars;
+  hipLaunchKernelGGL(debug_car_contact_kernel, dim3((num_envs + epb - 1) / epb), dim3(SBLOCK), CC_LDS_BYTES,
+                     (hipStream_t)stream, bodies, num_envs, num_cars, out, env_out);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -8,6 +8,7 @@
 #include "b2_oracle.h"
 #include <float.h>
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 /* ---- b2Settings.h ---- */
@@ -1164,4 +1165,126 @@ void or_collide(const float *cases, int n, float *out) {
         o[8] = m.pts[1].localPoint.x; o[9] = m.pts[1].localPoint.y;
         memcpy(&o[10], &m.pts[0].id, 4); memcpy(&o[11], &m.pts[1].id, 4);
     }
+}
+
+/* ---- car against car (tests/test_car_contact_cpu.py, tests/test_gpu_car_contact.py) ----
+   The build-only car-car extension has no counterpart in the reference (its cars never touch), so this is Box2D's own
+   algorithm for two DYNAMIC bodies, put together from this file's pieces: b2CollidePolygons on two car boxes,
+   b2WorldManifold::Initialize with both polygon radii, b2ContactSolver::InitializeVelocityConstraints and the
+   friction-then-normal point loops of SolveVelocityConstraints (rel_vel's association), with what the extension
+   states it leaves out: no warm start, no 2-point block solver (the one-point normal update runs per point), no
+   position correction.  Both bodies carry the car's mass and inertia; the fixtures mix to friction sqrt(0.7 * 0.7)
+   (0.7f exactly: a correctly rounded sqrtf undoes a float's square) and restitution max(0.1, 0.1).
+   bodies [E*C][7]: x y qs qc vx vy w.  Pairs (i, j), i < j, in lexicographic order; at most `cap` touching pairs are
+   kept per env, the rest counted as dropped; cull != 0 skips pairs whose centres lie more than 5.7 m apart on an axis.
+   out [E*C][4]: vx vy w jmax (the car's largest accumulated normal impulse); env_out [E][2]: solved, dropped;
+   pairs [E][cap][3]: i j pointCount; con [E][cap][12]: normal, world points 0 / 1, per point normalImpulse and
+   tangentImpulse, then per point the normal impulse the last friction pass clamped against: the one of the iteration
+   before, which the last normal pass may lower, down to 0 (pairs / con may be NULL; rows past `solved` are left
+   untouched). */
+typedef struct { int ia, ib, pointCount; ov2 normal, wp[2]; ovcp pts[2]; float clampImpulse[2]; } occ;
+__attribute__((visibility("default")))
+int or_car_contact(const float *bodies, int E, int C, int cap, int cull, float *out, int32_t *env_out, int32_t *pairs,
+                   float *con) {
+    if (E < 0 || C < 1 || cap < 0) return -1;
+    const float mA = CAR_INV_MASS, iA = CAR_INV_I, mB = CAR_INV_MASS, iB = CAR_INV_I;
+    const float friction = 0.7f, restitution = 0.1f;
+    const int velIters = 6;
+    opoly pa; car_poly(&pa);
+    occ *vc = (occ *)malloc(sizeof(occ) * (size_t)(cap > 0 ? cap : 1));
+    obodystate *b = (obodystate *)malloc(sizeof(obodystate) * (size_t)C);
+    oxf *xf = (oxf *)malloc(sizeof(oxf) * (size_t)C);
+    if (!vc || !b || !xf) { free(vc); free(b); free(xf); return -1; }
+    for (int e = 0; e < E; ++e) {
+        for (int i = 0; i < C; ++i) {
+            const float *k = bodies + ((size_t)e * C + i) * 7;
+            b[i].c = V(k[0], k[1]); b[i].a = 0.0f; b[i].v = V(k[4], k[5]); b[i].w = k[6];
+            xf[i].p = b[i].c; xf[i].q.s = k[2]; xf[i].q.c = k[3];
+        }
+        int n = 0, dropped = 0;
+        for (int i = 0; i < C; ++i)
+            for (int j = i + 1; j < C; ++j) {
+                if (cull && (fabsf(b[j].c.x - b[i].c.x) > 5.7f || fabsf(b[j].c.y - b[i].c.y) > 5.7f)) continue;
+                omanifold m; memset(&m, 0, sizeof(m));
+                collide_polygons(&m, &pa, xf[i], &pa, xf[j]);
+                if (m.pointCount == 0) continue;
+                if (n == cap) { ++dropped; continue; }
+                /* b2ContactSolver::InitializeVelocityConstraints, both bodies dynamic */
+                occ *v = &vc[n++];
+                memset(v, 0, sizeof(*v));
+                v->ia = i; v->ib = j; v->pointCount = m.pointCount;
+                world_manifold(&m, xf[i], POLY_RADIUS, xf[j], POLY_RADIUS, &v->normal, v->wp);
+                ov2 vA = b[i].v, vB = b[j].v; float wA = b[i].w, wB = b[j].w;
+                for (int q = 0; q < v->pointCount; ++q) {
+                    ovcp *p = &v->pts[q];
+                    p->rA = vsub(v->wp[q], b[i].c); p->rB = vsub(v->wp[q], b[j].c);
+                    float rnA = vcross(p->rA, v->normal), rnB = vcross(p->rB, v->normal);
+                    float kNormal = mA + mB + iA * rnA * rnA + iB * rnB * rnB;
+                    p->normalMass = kNormal > 0.0f ? 1.0f / kNormal : 0.0f;
+                    ov2 tangent = vcross_vs(v->normal, 1.0f);
+                    float rtA = vcross(p->rA, tangent), rtB = vcross(p->rB, tangent);
+                    float kTangent = mA + mB + iA * rtA * rtA + iB * rtB * rtB;
+                    p->tangentMass = kTangent > 0.0f ? 1.0f / kTangent : 0.0f;
+                    p->velocityBias = 0.0f;
+                    float vRel = vdot(v->normal, rel_vel(vA, wA, vB, wB, p));
+                    if (vRel < -VELOCITY_THRESHOLD) p->velocityBias = -restitution * vRel;
+                }
+            }
+        /* b2ContactSolver::SolveVelocityConstraints, velIters times, no warm start before it */
+        for (int it = 0; it < velIters; ++it)
+            for (int c = 0; c < n; ++c) {
+                occ *v = &vc[c];
+                obodystate *A = &b[v->ia], *B = &b[v->ib];
+                ov2 vA = A->v, vB = B->v; float wA = A->w, wB = B->w;
+                ov2 normal = v->normal, tangent = vcross_vs(normal, 1.0f);
+                for (int q = 0; q < v->pointCount; ++q) {
+                    ovcp *p = &v->pts[q];
+                    ov2 dv = rel_vel(vA, wA, vB, wB, p);
+                    float vt = vdot(dv, tangent);
+                    float lambda = p->tangentMass * (-vt);
+                    float maxFriction = friction * p->normalImpulse;
+                    v->clampImpulse[q] = p->normalImpulse;   /* (reported only) */
+                    float newImpulse = fclamp(p->tangentImpulse + lambda, -maxFriction, maxFriction);
+                    lambda = newImpulse - p->tangentImpulse;
+                    p->tangentImpulse = newImpulse;
+                    ov2 P = vmul(lambda, tangent);
+                    vA = vsub(vA, vmul(mA, P)); wA -= iA * vcross(p->rA, P);
+                    vB = vadd(vB, vmul(mB, P)); wB += iB * vcross(p->rB, P);
+                }
+                for (int q = 0; q < v->pointCount; ++q) {
+                    ovcp *p = &v->pts[q];
+                    ov2 dv = rel_vel(vA, wA, vB, wB, p);
+                    float vn = vdot(dv, normal);
+                    float lambda = -p->normalMass * (vn - p->velocityBias);
+                    float newImpulse = fmax_b2(p->normalImpulse + lambda, 0.0f);
+                    lambda = newImpulse - p->normalImpulse;
+                    p->normalImpulse = newImpulse;
+                    ov2 P = vmul(lambda, normal);
+                    vA = vsub(vA, vmul(mA, P)); wA -= iA * vcross(p->rA, P);
+                    vB = vadd(vB, vmul(mB, P)); wB += iB * vcross(p->rB, P);
+                }
+                A->v = vA; A->w = wA; B->v = vB; B->w = wB;
+            }
+        float *o = out + (size_t)e * C * 4;
+        for (int i = 0; i < C; ++i) { o[i * 4] = b[i].v.x; o[i * 4 + 1] = b[i].v.y; o[i * 4 + 2] = b[i].w; o[i * 4 + 3] = 0.0f; }
+        for (int c = 0; c < n; ++c) {   /* the listener's PostSolve: the largest normal impulse of the manifold */
+            const occ *v = &vc[c];
+            float jm = 0.0f;
+            for (int q = 0; q < v->pointCount; ++q) jm = fmax_b2(jm, v->pts[q].normalImpulse);
+            o[v->ia * 4 + 3] = fmax_b2(o[v->ia * 4 + 3], jm);
+            o[v->ib * 4 + 3] = fmax_b2(o[v->ib * 4 + 3], jm);
+            if (pairs) { int32_t *r = pairs + ((size_t)e * cap + c) * 3; r[0] = v->ia; r[1] = v->ib; r[2] = v->pointCount; }
+            if (con) {
+                float *r = con + ((size_t)e * cap + c) * 12;
+                r[0] = v->normal.x; r[1] = v->normal.y;
+                r[2] = v->wp[0].x; r[3] = v->wp[0].y; r[4] = v->wp[1].x; r[5] = v->wp[1].y;
+                r[6] = v->pts[0].normalImpulse; r[7] = v->pts[0].tangentImpulse;
+                r[8] = v->pts[1].normalImpulse; r[9] = v->pts[1].tangentImpulse;
+                r[10] = v->clampImpulse[0]; r[11] = v->clampImpulse[1];
+            }
+        }
+        env_out[e * 2] = n; env_out[e * 2 + 1] = dropped;
+    }
+    free(vc); free(b); free(xf);
+    return 0;
 }

@@ -60,8 +60,32 @@ def lib():
         L.or_toi.argtypes = [f32p, ctypes.c_int, f32p, ctypes.POINTER(ctypes.c_int32)]
         L.or_collide.restype = None
         L.or_collide.argtypes = [f32p, ctypes.c_int, f32p]
+        L.or_car_contact.restype = ctypes.c_int
+        L.or_car_contact.argtypes = [f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, f32p,
+                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), f32p]
         _lib = L
     return _lib
+
+
+def car_contact(bodies, C, cap=None, cull=True):
+    """or_car_contact on bodies [E*C, 7] float32 (x y qs qc vx vy w), C cars per env, at most `cap` touching pairs kept
+    per env (default C, the engine's cap) in (i, j) order, the 5.7 m centre cull on or off.  Returns a dict: out
+    [E, C, 4] float32 (vx vy w jmax), solved / dropped [E] int32, pairs [E, cap, 3] int32 (i j pointCount) and con
+    [E, cap, 12] float32 (normal, world points 0 / 1, normalImpulse / tangentImpulse of point 0, of point 1, the normal
+    impulse the last friction pass clamped against for point 0, for point 1); rows of pairs / con past `solved` are
+    zero."""
+    bodies = np.ascontiguousarray(bodies, np.float32).reshape(-1, 7)
+    assert len(bodies) % C == 0, (len(bodies), C)
+    E = len(bodies) // C
+    cap = C if cap is None else int(cap)
+    out = np.zeros((E, C, 4), np.float32)
+    env_out = np.zeros((E, 2), np.int32)
+    pairs = np.zeros((E, max(cap, 1), 3), np.int32)
+    con = np.zeros((E, max(cap, 1), 12), np.float32)
+    rc = lib().or_car_contact(_p(bodies, ctypes.c_float), E, C, cap, int(bool(cull)), _p(out, ctypes.c_float),
+                              _p(env_out, ctypes.c_int32), _p(pairs, ctypes.c_int32), _p(con, ctypes.c_float))
+    assert rc == 0, rc
+    return dict(out=out, solved=env_out[:, 0].copy(), dropped=env_out[:, 1].copy(), pairs=pairs, con=con)
 
 
 def toi(cases):
