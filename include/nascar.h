@@ -299,7 +299,8 @@ int nascar_set_actor(NascarHandle* h, const float* w1, const float* b1, const fl
  * bf16-operand MFMA kernel (fp32 accumulation; ~8x faster: 16.2 vs 135 us at 81 920 observations, max |delta action|
  * 0.40 on sac_1235). */
 int nascar_set_actor_precision(NascarHandle* h, int32_t fp32);
-/* The loaded actor on any device batch: obs [n][38] float32 -> actions [n][2] float32 (both 8-byte aligned). */
+/* The loaded actor on any device batch: obs [n][38] float32 -> actions [n][2] float32 (both 8-byte aligned).  n = 0
+ * launches nothing and returns 0; the pointers of an empty batch may be null (nascar_controller_forward likewise). */
 int nascar_actor_forward(NascarHandle* h, const float* obs, int32_t n, float* actions, void* stream);
 
 /* Per-car controllers: the reference's race modes put a different controller in every car of an env

@@ -5183,10 +5183,11 @@ static void launch_actor(NascarHandle* h, int n, const float* obs, float* action
 
 // Actor forward on an arbitrary device batch: obs [n][38] float32 -> actions [n][2] float32.
 extern "C" int nascar_actor_forward(NascarHandle* h, const float* obs, int32_t n, float* actions, void* stream) {
-  if (!h || !obs || !actions || n < 0) return fail("bad argument");
+  if (!h || n < 0) return fail("bad argument");
   if (!h->d_actor) return fail("no actor loaded (nascar_set_actor)");
+  if (n == 0) return 0;   // an empty batch has no buffers: its pointers may be null
+  if (!obs || !actions) return fail("bad argument");
   if (((uintptr_t)obs | (uintptr_t)actions) & 7) return fail("actor obs/actions must be 8-byte aligned");
-  if (n == 0) return 0;
   launch_actor(h, n, obs, actions, stream);
   HIPCHK(hipGetLastError());
   return 0;
@@ -5324,10 +5325,11 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
 }
 extern "C" int nascar_controller_forward(NascarHandle* h, int32_t id, const float* obs, int32_t n, float* actions,
                                          void* stream) {
-  if (!h || !obs || !actions || n < 0) return fail("bad argument");
+  if (!h || n < 0) return fail("bad argument");
   if (id < 0 || id >= (int)h->ctrl.size()) return fail("unknown controller id %d (%d loaded)", id, (int)h->ctrl.size());
+  if (n == 0) return 0;   // an empty batch has no buffers: its pointers may be null
+  if (!obs || !actions) return fail("bad argument");
   if ((uintptr_t)actions & 7) return fail("controller actions must be 8-byte aligned");
-  if (n == 0) return 0;
   const MlpDev& K = h->ctrl[id];
   MlpLaunch L{};   // a flat batch: n envs of one car slot
   L.table = h->d_ctrl; L.obs = obs; L.act = actions; L.env0 = 0; L.nenv = n; L.C = 1;
