@@ -34,305 +34,8 @@
 #include "nascar_actor.h"
 #include "nascar_rays.h"
 
-#pragma clang fp contract(off)
-
-using namespace nascar;
-
-#define MAX_SEG 64
-
-#ifdef NASCAR_DEBUG
-__device__ double* g_dbg = nullptr;   // debug build only: intermediate taps of one car
-__device__ int g_dbg_car = -1;
-#define DBG(n, slot, val) do { if ((n) == g_dbg_car && g_dbg) g_dbg[slot] = (double)(val); } while (0)
-#else
-#define DBG(n, slot, val) do { } while (0)
-#endif
-
-
-// ------------------------------------------------------------------ device-side tables
-struct DSeg {   // per segment, float64 (src/track_generator.py TrackSegment)
-  double sx, sy, ex, ey, width, banking, la, chord;  // la: banking lateral assist (src/car.py:527-533)
-};
-// Ray-candidate lists ("beams"), built on the host (build_beams): for every cell (nascar_set_beam_cell) near the
-// walls and every one of BEAM_NB direction bins, the walls that a ray starting anywhere in the cell with a
-// direction in the bin can reach within 250 m, sorted by a lower bound of their distance from the cell.
-// Entry (16 bits) = bound code << wbits | wall index (wbits = 10 up to 1024 walls, up to 13 for 8192): code c stands
-// for the bound c^2 * kq m, rounded down from the wall's exact bound (c < cmax = 2^(16 - wbits) - 1, the sentinel's
-// code, past every hit), so the codes are conservative and ascend along a list.  A ray walks its list and stops at the first entry whose bound exceeds its best hit so far: the minimum exact
-// fraction over the walls visited is the minimum over all walls, i.e. the reference's Box2D RayCast result.
-#define BEAM_NB 256       // direction bins (measured 64: 44.2 us, 128: 41.7, 256: 38.7, 512: 39.1) (a multiple of 16: ray i is BEAM_NB / 16 bins from ray i + 1)
-#define BEAM_STRIDE (BEAM_NB / 16)
-// list slot of a bin: the 16 bins of one residue mod BEAM_STRIDE are adjacent, so a car's 16 rays read
-// 16 adjacent lists
-__host__ __device__ __forceinline__ int beam_slot(int bin) { return (bin % BEAM_STRIDE) * 16 + bin / BEAM_STRIDE; }
-__host__ __device__ __forceinline__ int beam_bin(int slot) { return (slot % 16) * BEAM_STRIDE + slot / 16; }
-#define BEAM_MAX_WALL_BITS 13                  // tracks with more than 8192 walls get no lists (the wall-group walk)
-#define BEAM_PAD 0xFFFFu                       // sentinel: the largest code, stops every walk
-#define BEAM_CONT_MAX 0xFFFFu                  // continuation entries of one cell (16-bit offsets from the cell's base)
-struct BeamGrid {
-  float ox, oy, inv_cell; int nx, ny;
-  uint32_t wbits, wmask, cmax; float kq;   // entry layout: wall index bits, their mask, sentinel code, bound scale (m)
-  // the cell map in chunks of BEAM_CHUNK cells along x, [ny][nxc]: (first list of the chunk's first built cell = its
-  // id * BEAM_NB, the chunk's first ent[] index, the mask of its built cells, 0) -- the built cells of a chunk have
-  // consecutive ids, so a cell's list base is the chunk's plus BEAM_NB per built cell below it.  ~0.5 MB per track
-  // (a dense int2 per cell was ~9 MB, a random 128-byte line per car that no L2 held; this table stays cached)
-  const int4* chunk; int nxc;
-  const uint16_t* ent;      // list continuations, each closed by a BEAM_PAD sentinel
-  // [built cells * BEAM_NB] 8-byte head records: the first BEAM_HEAD entries of each list (padded with BEAM_PAD) and
-  // the offset + 1 of the list's continuation from its chunk's first ent[] index (0: none), so a walk starts with one
-  // 8-byte load and reads the rest in chunks of RAY_CHUNK entries up to the sentinel.  (Round 5's 16-byte heads held
-  // three 32-bit entries and an absolute index: 256 B of heads per car and step against 128.)
-  const uint2* head;
-};
-#define BEAM_HEAD 3
-#define RAY_CHUNK 4    // list entries past the head requested together
-// an entry's distance bound in m (the sentinel's: beyond every hit) and its wall
-__device__ __forceinline__ float beam_bound(const BeamGrid& G, uint32_t v) {
-  const uint32_t c = v >> G.wbits;
-  return c >= G.cmax ? 1e30f : (float)(c * c) * G.kq;
-}
-__device__ __forceinline__ int beam_wall(const BeamGrid& G, uint32_t v) { return (int)(v & G.wmask); }
-// a walk goes on past an entry while its bound is within the best hit (fraction bi of the 250 m ray), with margin
-__device__ __forceinline__ bool beam_beyond(const BeamGrid& G, uint32_t v, float bi) {
-  return beam_bound(G, v) > bi * 250.0f * 1.00001f + 0.01f;
-}
-#define BEAM_CHUNK 32
-struct BeamHead { uint2 w; uint32_t cb; };   // the head record and its chunk's first ent[] index
-__device__ __forceinline__ BeamHead beam_head(const BeamGrid& G, int2 cell, int li) {
-  BeamHead h;
-  h.w = ldg(G.head + li);
-  h.cb = (uint32_t)cell.y;
-  return h;
-}
-#define LDS_PER_CU ((size_t)160 * 1024)   // gfx950: 160 KiB of LDS per CU, all of which one workgroup may declare
-struct TrackDev {
-  LWall* walls; int nwall;
-  const float4* wfat;  // [nwall] broadphase fat AABBs
-  DSeg* segs; int nseg;
-  double* prefix;      // cumulative chord length before segment k (src/car_env.py:1593-1600)
-  double total_length; int startline; int has_banking;
-  WallGrid bp, sn;
-  const float4* groups; int ngroup;   // sensor wall groups: (cx, cy, radius incl. margin, first | count << 16)
-  const float4* swall;                // [2 * nwall] sensor image: (px, py, rad + 0.25, hx), (qs, qc, hy, 0)
-  BeamGrid beam;                      // per (cell, direction bin) candidate walls of one ray (ray_sensor_kernel)
-};
-
-struct Params {
-  int E, C, N, epb, nblocks, reset_on_lap;
-  float dt_f; double dt_d; float friction;
-  double start_x, start_y; float start_angle;
-  float* f32; double* f64; int* i32; double* acc;
-  DContact* ct; int* act_key; float* act_n;
-  double* env_time; int* env_i32;
-  const int* blk_track; const int* blk_env;
-  const TrackDev* tracks;
-  float4* pose;        // [2][N] sensor hand-off: (x, y, angle, mode) -- see sensor_kernel
-  // [E] this step's auto-reset envs (the logic writes every env's byte): the step's sensor passes read an env's pass-B
-  // pose only when its byte is set, so the pass-B records of the other cars are neither cleared nor read every step
-  uint8_t* reset_env;
-  double2* pose_cs;    // [2][N] cos, sin of (double)angle for the ray end points (computed once per car)
-  const double2* ray_cs;   // [16] cos, sin of the ray offsets radians(22.5 i) (nascar_rays.h)
-  double* ctl;         // [N][4] rule-driver state of the device action sources (policy_car)
-  float* vhist;        // [VH_RING][N] speed history for validate_performance, or null (nascar_set_perf_history)
-  int car_contact;     // build-only extension (nascar_set_car_contact): car-car contact inside each env; 0 = reference
-  // block map shortcuts (prepare()): map_identity = blk_env[s] is s (< E) or -1, one_track >= 0 = every
-  // block's track; they spare each kernel's first dependent load
-  int map_identity, one_track;
-  int blk0;            // first step-kernel workgroup of this launch (sharded rollout, nascar_set_rollout_streams); else 0
-};
-__device__ __forceinline__ int blk_env_of(const Params& P, int el, int s) {
-  if (el >= P.epb) return -1;
-  if (P.map_identity) return s < P.E ? s : -1;
-  return P.blk_env[s];
-}
-__device__ __forceinline__ int blk_track_of(const Params& P, int b) { return P.one_track >= 0 ? P.one_track : P.blk_track[b]; }
-// a workgroup of no track: the device-built block map's workgroups past the last track's (random-track mode); every
-// kernel returns first for them (never taken with the host-built map, whose workgroups all hold envs)
-__device__ __forceinline__ bool blk_empty(const Params& P, int b) { return P.one_track < 0 && P.blk_track[b] < 0; }
-// The step kernels' workgroup (block-map index) of this dispatch slot.  The dispatcher deals a launch's workgroups
-// round-robin over the 8 XCDs (slot b on XCD b % 8), each with its own L2; remapped here, each XCD takes a contiguous
-// run of the launch's workgroups instead, so the state cache lines two neighbouring workgroups share (a workgroup's
-// SoA run of cars rarely ends on a 128-B line) are fetched into one L2, not two.
-__device__ __forceinline__ int wg_block(const Params& P) {
-  const int nb = gridDim.x, b = blockIdx.x, q = nb >> 3, r = nb & 7, x = b & 7;
-  return P.blk0 + x * q + min(x, r) + (b >> 3);
-}
-// BeamGrid record of the cell holding (x, y): (list base = built cell id * BEAM_NB, its chunk's first ent[] index);
-// list base -1 outside the built cells
-__device__ __forceinline__ int2 beam_cell(const BeamGrid& G, float x, float y) {
-  const float fx = (x - G.ox) * G.inv_cell, fy = (y - G.oy) * G.inv_cell;
-  if (!(fx >= 0.0f && fy >= 0.0f && fx < (float)G.nx && fy < (float)G.ny)) return make_int2(-1, 0);
-  const int cx = (int)fx;
-  const int4 ch = ldg(G.chunk + (int)fy * G.nxc + cx / BEAM_CHUNK);
-  const uint32_t bit = 1u << (cx % BEAM_CHUNK), m = (uint32_t)ch.z;
-  if (!(m & bit)) return make_int2(-1, 0);
-  return make_int2(ch.x + __popc(m & (bit - 1u)) * BEAM_NB, ch.y);
-}
-
-#define F32P(P, f) ((P).f32 + (size_t)F32_##f * (P).N)
-#define F64P(P, f) ((P).f64 + (size_t)F64_##f * (P).N)
-#define I32P(P, f) ((P).i32 + (size_t)I32_##f * (P).N)
-
-// ------------------------------------------------------------------ load / store of one car
-__device__ inline void car_load(const Params& P, int n, Car& c) {
-  c.c = V(F32P(P, cx)[n], F32P(P, cy)[n]); c.a = F32P(P, a)[n];
-  c.v = V(F32P(P, vx)[n], F32P(P, vy)[n]); c.w = F32P(P, w)[n];
-  c.xf.q.s = F32P(P, qs)[n]; c.xf.q.c = F32P(P, qc)[n]; c.xf.p = V(F32P(P, xpx)[n], F32P(P, xpy)[n]);
-  c.sleep = F32P(P, sleep)[n]; c.invdt0 = F32P(P, invdt0)[n];
-  c.fat.lo = V(F32P(P, flox)[n], F32P(P, floy)[n]); c.fat.hi = V(F32P(P, fhix)[n], F32P(P, fhiy)[n]);
-  c.cum_reward = F32P(P, cum_reward)[n]; c.cum_reward_info = F32P(P, cum_reward_info)[n];
-  c.rpm = F64P(P, rpm)[n]; c.pvx = F64P(P, pvx)[n]; c.pvy = F64P(P, pvy)[n];
-  c.lfm = F64P(P, lfm)[n]; c.slip = F64P(P, slip)[n]; c.bank = F64P(P, bank)[n];
-  c.load[0] = F64P(P, load0)[n]; c.load[1] = F64P(P, load1)[n]; c.load[2] = F64P(P, load2)[n]; c.load[3] = F64P(P, load3)[n];
-  c.temp[0] = F64P(P, temp0)[n]; c.temp[1] = F64P(P, temp1)[n]; c.temp[2] = F64P(P, temp2)[n]; c.temp[3] = F64P(P, temp3)[n];
-  c.wear[0] = F64P(P, wear0)[n]; c.wear[1] = F64P(P, wear1)[n]; c.wear[2] = F64P(P, wear2)[n]; c.wear[3] = F64P(P, wear3)[n];
-  c.imp = F64P(P, imp)[n];
-  c.lt_start = F64P(P, lt_start)[n]; c.lt_cur = F64P(P, lt_cur)[n]; c.lt_last = F64P(P, lt_last)[n];
-  c.lt_best = F64P(P, lt_best)[n]; c.lt_px = F64P(P, lt_px)[n]; c.lt_py = F64P(P, lt_py)[n]; c.lt_dist = F64P(P, lt_dist)[n];
-  c.cum_impact = F64P(P, cum_impact)[n]; c.stuck_dur = F64P(P, stuck_dur)[n];
-  c.stuck_sx = F64P(P, stuck_sx)[n]; c.stuck_sy = F64P(P, stuck_sy)[n];
-  c.prev_px = F64P(P, prev_px)[n]; c.prev_py = F64P(P, prev_py)[n];
-  c.prog_hist = F64P(P, prog_hist)[n]; c.back = F64P(P, back)[n]; c.prev_back = F64P(P, prev_back)[n];
-  c.imp_at_obs = F64P(P, imp_at_obs)[n];
-  c.awake = I32P(P, awake)[n]; c.nct = I32P(P, nct)[n]; c.overflow = I32P(P, overflow)[n];
-  c.acc_len = I32P(P, acc_len)[n]; c.acc_head = I32P(P, acc_head)[n];
-  c.imp_present = I32P(P, imp_present)[n]; c.nact = I32P(P, nact)[n];
-  c.lt_timing = I32P(P, lt_timing)[n]; c.lt_has_last = I32P(P, lt_has_last)[n]; c.lt_has_best = I32P(P, lt_has_best)[n];
-  c.lt_crossed = I32P(P, lt_crossed)[n]; c.lt_has_pos = I32P(P, lt_has_pos)[n]; c.lt_laps = I32P(P, lt_laps)[n];
-  c.disabled = I32P(P, disabled)[n]; c.has_stuck_start = I32P(P, has_stuck_start)[n];
-  c.first_step = I32P(P, first_step)[n]; c.prev_laps = I32P(P, prev_laps)[n];
-  c.just_disabled = 0;
-  c.force = zero2(); c.torque = 0.0f; c.c0 = c.c; c.a0 = c.a; c.alpha0 = 0.0f; c.moved = 0;
-  c.ct = P.ct + (size_t)n * MAXC; c.act_key = P.act_key + (size_t)n * MAXC; c.act_n = P.act_n + (size_t)n * MAXC * 2;
-  c.acc = nullptr;
-}
-__device__ inline void car_store(const Params& P, int n, const Car& c) {
-  F32P(P, cx)[n] = c.c.x; F32P(P, cy)[n] = c.c.y; F32P(P, a)[n] = c.a;
-  F32P(P, vx)[n] = c.v.x; F32P(P, vy)[n] = c.v.y; F32P(P, w)[n] = c.w;
-  F32P(P, qs)[n] = c.xf.q.s; F32P(P, qc)[n] = c.xf.q.c; F32P(P, xpx)[n] = c.xf.p.x; F32P(P, xpy)[n] = c.xf.p.y;
-  F32P(P, sleep)[n] = c.sleep; F32P(P, invdt0)[n] = c.invdt0;
-  F32P(P, flox)[n] = c.fat.lo.x; F32P(P, floy)[n] = c.fat.lo.y; F32P(P, fhix)[n] = c.fat.hi.x; F32P(P, fhiy)[n] = c.fat.hi.y;
-  F32P(P, cum_reward)[n] = c.cum_reward; F32P(P, cum_reward_info)[n] = c.cum_reward_info;
-  F64P(P, rpm)[n] = c.rpm; F64P(P, pvx)[n] = c.pvx; F64P(P, pvy)[n] = c.pvy;
-  F64P(P, lfm)[n] = c.lfm; F64P(P, slip)[n] = c.slip; F64P(P, bank)[n] = c.bank;
-  F64P(P, load0)[n] = c.load[0]; F64P(P, load1)[n] = c.load[1]; F64P(P, load2)[n] = c.load[2]; F64P(P, load3)[n] = c.load[3];
-  F64P(P, temp0)[n] = c.temp[0]; F64P(P, temp1)[n] = c.temp[1]; F64P(P, temp2)[n] = c.temp[2]; F64P(P, temp3)[n] = c.temp[3];
-  F64P(P, wear0)[n] = c.wear[0]; F64P(P, wear1)[n] = c.wear[1]; F64P(P, wear2)[n] = c.wear[2]; F64P(P, wear3)[n] = c.wear[3];
-  F64P(P, imp)[n] = c.imp;
-  F64P(P, lt_start)[n] = c.lt_start; F64P(P, lt_cur)[n] = c.lt_cur; F64P(P, lt_last)[n] = c.lt_last;
-  F64P(P, lt_best)[n] = c.lt_best; F64P(P, lt_px)[n] = c.lt_px; F64P(P, lt_py)[n] = c.lt_py; F64P(P, lt_dist)[n] = c.lt_dist;
-  F64P(P, cum_impact)[n] = c.cum_impact; F64P(P, stuck_dur)[n] = c.stuck_dur;
-  F64P(P, stuck_sx)[n] = c.stuck_sx; F64P(P, stuck_sy)[n] = c.stuck_sy;
-  F64P(P, prev_px)[n] = c.prev_px; F64P(P, prev_py)[n] = c.prev_py;
-  F64P(P, prog_hist)[n] = c.prog_hist; F64P(P, back)[n] = c.back; F64P(P, prev_back)[n] = c.prev_back;
-  F64P(P, imp_at_obs)[n] = c.imp_at_obs;
-  I32P(P, awake)[n] = c.awake; I32P(P, nct)[n] = c.nct; I32P(P, overflow)[n] = c.overflow;
-  I32P(P, acc_len)[n] = c.acc_len; I32P(P, acc_head)[n] = c.acc_head;
-  I32P(P, imp_present)[n] = c.imp_present; I32P(P, nact)[n] = c.nact;
-  I32P(P, lt_timing)[n] = c.lt_timing; I32P(P, lt_has_last)[n] = c.lt_has_last; I32P(P, lt_has_best)[n] = c.lt_has_best;
-  I32P(P, lt_crossed)[n] = c.lt_crossed; I32P(P, lt_has_pos)[n] = c.lt_has_pos; I32P(P, lt_laps)[n] = c.lt_laps;
-  I32P(P, disabled)[n] = c.disabled; I32P(P, has_stuck_start)[n] = c.has_stuck_start;
-  I32P(P, first_step)[n] = c.first_step; I32P(P, prev_laps)[n] = c.prev_laps;
-}
-
-// Staged load/store for model_kernel: only the body, vehicle-model and listener fields are
-// live through update_physics + the Box2D step; the model fields are written back right
-// after update_physics (a compiler memory barrier stops the reload being forwarded) and the
-// lap-timer / bookkeeping fields are loaded after the Box2D step.  Register pressure, not
-// traffic, is what this buys (the re-read hits L2).
-__device__ inline void car_load_phys(const Params& P, int n, Car& c) {
-  c.c = V(F32P(P, cx)[n], F32P(P, cy)[n]); c.a = F32P(P, a)[n];
-  c.v = V(F32P(P, vx)[n], F32P(P, vy)[n]); c.w = F32P(P, w)[n];
-  c.xf.q.s = F32P(P, qs)[n]; c.xf.q.c = F32P(P, qc)[n]; c.xf.p = V(F32P(P, xpx)[n], F32P(P, xpy)[n]);
-  c.sleep = F32P(P, sleep)[n]; c.invdt0 = F32P(P, invdt0)[n];
-  c.fat.lo = V(F32P(P, flox)[n], F32P(P, floy)[n]); c.fat.hi = V(F32P(P, fhix)[n], F32P(P, fhiy)[n]);
-  c.rpm = F64P(P, rpm)[n]; c.pvx = F64P(P, pvx)[n]; c.pvy = F64P(P, pvy)[n];
-  c.lfm = F64P(P, lfm)[n]; c.slip = F64P(P, slip)[n]; c.bank = F64P(P, bank)[n];
-  c.load[0] = F64P(P, load0)[n]; c.load[1] = F64P(P, load1)[n]; c.load[2] = F64P(P, load2)[n]; c.load[3] = F64P(P, load3)[n];
-  c.temp[0] = F64P(P, temp0)[n]; c.temp[1] = F64P(P, temp1)[n]; c.temp[2] = F64P(P, temp2)[n]; c.temp[3] = F64P(P, temp3)[n];
-  c.wear[0] = F64P(P, wear0)[n]; c.wear[1] = F64P(P, wear1)[n]; c.wear[2] = F64P(P, wear2)[n]; c.wear[3] = F64P(P, wear3)[n];
-  c.imp = F64P(P, imp)[n];
-  c.awake = I32P(P, awake)[n]; c.nct = I32P(P, nct)[n]; c.overflow = I32P(P, overflow)[n];
-  c.acc_len = I32P(P, acc_len)[n]; c.acc_head = I32P(P, acc_head)[n];
-  c.imp_present = I32P(P, imp_present)[n]; c.nact = I32P(P, nact)[n];
-  c.disabled = I32P(P, disabled)[n];
-  c.just_disabled = 0;
-  c.force = zero2(); c.torque = 0.0f; c.c0 = c.c; c.a0 = c.a; c.alpha0 = 0.0f; c.moved = 0;
-  c.ct = P.ct + (size_t)n * MAXC; c.act_key = P.act_key + (size_t)n * MAXC; c.act_n = P.act_n + (size_t)n * MAXC * 2;
-  c.acc = nullptr;
-}
-__device__ inline void car_store_model(const Params& P, int n, const Car& c) {
-  F64P(P, rpm)[n] = c.rpm; F64P(P, pvx)[n] = c.pvx; F64P(P, pvy)[n] = c.pvy;
-  F64P(P, lfm)[n] = c.lfm; F64P(P, slip)[n] = c.slip;
-  F64P(P, load0)[n] = c.load[0]; F64P(P, load1)[n] = c.load[1]; F64P(P, load2)[n] = c.load[2]; F64P(P, load3)[n] = c.load[3];
-  F64P(P, temp0)[n] = c.temp[0]; F64P(P, temp1)[n] = c.temp[1]; F64P(P, temp2)[n] = c.temp[2]; F64P(P, temp3)[n] = c.temp[3];
-  F64P(P, wear0)[n] = c.wear[0]; F64P(P, wear1)[n] = c.wear[1]; F64P(P, wear2)[n] = c.wear[2]; F64P(P, wear3)[n] = c.wear[3];
-  I32P(P, acc_len)[n] = c.acc_len; I32P(P, acc_head)[n] = c.acc_head;
-}
-__device__ inline void car_reload_tyres(const Params& P, int n, Car& c) {
-  c.load[0] = F64P(P, load0)[n]; c.load[1] = F64P(P, load1)[n]; c.load[2] = F64P(P, load2)[n]; c.load[3] = F64P(P, load3)[n];
-  c.temp[0] = F64P(P, temp0)[n]; c.temp[1] = F64P(P, temp1)[n]; c.temp[2] = F64P(P, temp2)[n]; c.temp[3] = F64P(P, temp3)[n];
-  c.wear[0] = F64P(P, wear0)[n]; c.wear[1] = F64P(P, wear1)[n]; c.wear[2] = F64P(P, wear2)[n]; c.wear[3] = F64P(P, wear3)[n];
-}
-__device__ inline void car_load_logic(const Params& P, int n, Car& c) {
-  c.cum_reward = F32P(P, cum_reward)[n]; c.cum_reward_info = F32P(P, cum_reward_info)[n];
-  c.lt_start = F64P(P, lt_start)[n]; c.lt_cur = F64P(P, lt_cur)[n]; c.lt_last = F64P(P, lt_last)[n];
-  c.lt_best = F64P(P, lt_best)[n]; c.lt_px = F64P(P, lt_px)[n]; c.lt_py = F64P(P, lt_py)[n]; c.lt_dist = F64P(P, lt_dist)[n];
-  c.cum_impact = F64P(P, cum_impact)[n]; c.stuck_dur = F64P(P, stuck_dur)[n];
-  c.stuck_sx = F64P(P, stuck_sx)[n]; c.stuck_sy = F64P(P, stuck_sy)[n];
-  c.prev_px = F64P(P, prev_px)[n]; c.prev_py = F64P(P, prev_py)[n];
-  c.prog_hist = F64P(P, prog_hist)[n]; c.back = F64P(P, back)[n]; c.prev_back = F64P(P, prev_back)[n];
-  c.imp_at_obs = F64P(P, imp_at_obs)[n];
-  c.lt_timing = I32P(P, lt_timing)[n]; c.lt_has_last = I32P(P, lt_has_last)[n]; c.lt_has_best = I32P(P, lt_has_best)[n];
-  c.lt_crossed = I32P(P, lt_crossed)[n]; c.lt_has_pos = I32P(P, lt_has_pos)[n]; c.lt_laps = I32P(P, lt_laps)[n];
-  c.has_stuck_start = I32P(P, has_stuck_start)[n];
-  c.first_step = I32P(P, first_step)[n]; c.prev_laps = I32P(P, prev_laps)[n];
-}
-
-// model_kernel -> logic_kernel hand-off: the body / listener fields the Box2D step produced
-__device__ inline void car_store_body(const Params& P, int n, const Car& c) {
-  F32P(P, cx)[n] = c.c.x; F32P(P, cy)[n] = c.c.y; F32P(P, a)[n] = c.a;
-  F32P(P, vx)[n] = c.v.x; F32P(P, vy)[n] = c.v.y; F32P(P, w)[n] = c.w;
-  F32P(P, qs)[n] = c.xf.q.s; F32P(P, qc)[n] = c.xf.q.c; F32P(P, xpx)[n] = c.xf.p.x; F32P(P, xpy)[n] = c.xf.p.y;
-  F32P(P, sleep)[n] = c.sleep; F32P(P, invdt0)[n] = c.invdt0;
-  F32P(P, flox)[n] = c.fat.lo.x; F32P(P, floy)[n] = c.fat.lo.y; F32P(P, fhix)[n] = c.fat.hi.x; F32P(P, fhiy)[n] = c.fat.hi.y;
-  F64P(P, imp)[n] = c.imp;
-  I32P(P, awake)[n] = c.awake; I32P(P, nct)[n] = c.nct; I32P(P, overflow)[n] = c.overflow;
-  I32P(P, imp_present)[n] = c.imp_present; I32P(P, nact)[n] = c.nact;
-}
-__device__ inline void car_load_body(const Params& P, int n, Car& c) {
-  c.c = V(F32P(P, cx)[n], F32P(P, cy)[n]); c.a = F32P(P, a)[n];
-  c.v = V(F32P(P, vx)[n], F32P(P, vy)[n]); c.w = F32P(P, w)[n];
-  c.xf.q.s = F32P(P, qs)[n]; c.xf.q.c = F32P(P, qc)[n]; c.xf.p = V(F32P(P, xpx)[n], F32P(P, xpy)[n]);
-  c.sleep = F32P(P, sleep)[n]; c.invdt0 = F32P(P, invdt0)[n];
-  c.fat.lo = V(F32P(P, flox)[n], F32P(P, floy)[n]); c.fat.hi = V(F32P(P, fhix)[n], F32P(P, fhiy)[n]);
-  c.imp = F64P(P, imp)[n];
-  c.awake = I32P(P, awake)[n]; c.nct = I32P(P, nct)[n]; c.overflow = I32P(P, overflow)[n];
-  c.imp_present = I32P(P, imp_present)[n]; c.nact = I32P(P, nact)[n];
-  c.disabled = I32P(P, disabled)[n];
-  c.just_disabled = 0;
-  c.force = zero2(); c.torque = 0.0f; c.c0 = c.c; c.a0 = c.a; c.alpha0 = 0.0f; c.moved = 0;
-  c.ct = P.ct + (size_t)n * MAXC; c.act_key = P.act_key + (size_t)n * MAXC; c.act_n = P.act_n + (size_t)n * MAXC * 2;
-  c.acc = nullptr;
-}
-// logic_kernel's write-back: every field but the vehicle-model ones (car_store_model) and the body
-// ones only the model kernel changes
-__device__ inline void car_store_logic(const Params& P, int n, const Car& c) {
-  F32P(P, cum_reward)[n] = c.cum_reward; F32P(P, cum_reward_info)[n] = c.cum_reward_info;
-  F64P(P, bank)[n] = c.bank; F64P(P, imp)[n] = c.imp;
-  F64P(P, lt_start)[n] = c.lt_start; F64P(P, lt_cur)[n] = c.lt_cur; F64P(P, lt_last)[n] = c.lt_last;
-  F64P(P, lt_best)[n] = c.lt_best; F64P(P, lt_px)[n] = c.lt_px; F64P(P, lt_py)[n] = c.lt_py; F64P(P, lt_dist)[n] = c.lt_dist;
-  F64P(P, cum_impact)[n] = c.cum_impact; F64P(P, stuck_dur)[n] = c.stuck_dur;
-  F64P(P, stuck_sx)[n] = c.stuck_sx; F64P(P, stuck_sy)[n] = c.stuck_sy;
-  F64P(P, prev_px)[n] = c.prev_px; F64P(P, prev_py)[n] = c.prev_py;
-  F64P(P, prog_hist)[n] = c.prog_hist; F64P(P, back)[n] = c.back; F64P(P, prev_back)[n] = c.prev_back;
-  F64P(P, imp_at_obs)[n] = c.imp_at_obs;
-  I32P(P, imp_present)[n] = c.imp_present;
-  I32P(P, lt_timing)[n] = c.lt_timing; I32P(P, lt_has_last)[n] = c.lt_has_last; I32P(P, lt_has_best)[n] = c.lt_has_best;
-  I32P(P, lt_crossed)[n] = c.lt_crossed; I32P(P, lt_has_pos)[n] = c.lt_has_pos; I32P(P, lt_laps)[n] = c.lt_laps;
-  I32P(P, disabled)[n] = c.disabled; I32P(P, has_stuck_start)[n] = c.has_stuck_start;
-  I32P(P, first_step)[n] = c.first_step; I32P(P, prev_laps)[n] = c.prev_laps;
-}
+#include "nascar_params.h"
+#include "nascar_car_io.h"
 
 // ------------------------------------------------------------------ tyres (src/tyre.py, src/tyre_manager.py)
 __device__ inline double tyre_grip(double T, double wear) {
@@ -1968,14 +1671,11 @@ __device__ __forceinline__ void model_block(const Params& P, const void* actions
 }
 __global__ void __launch_bounds__(SBLOCK) __attribute__((amdgpu_waves_per_eu(MODEL_WPE))) model_kernel(Params P, const void* actions, int discrete, int want_term,
                                                                                                     int policy, uint64_t seed, int64_t step, const float* pobs) {
-  const int tid = threadIdx.x, C = P.C;
-  const int el = tid / C, car = tid - el * C;
-  const int slot = wg_block(P) * P.epb + el;
-  const int env = blk_env_of(P, el, slot);
+  const CarSlot s = car_slot(P, wg_block(P));
   if (blk_empty(P, wg_block(P))) return;   // empty workgroup (device-built block map)
   Car c;
   SegReg sr;
-  model_block<false>(P, actions, discrete, want_term, policy, seed, step, pobs, tid, env, env >= 0 ? env * C + car : 0, c, sr);
+  model_block<false>(P, actions, discrete, want_term, policy, seed, step, pobs, s.tid, s.env, s.n, c, sr);
 }
 
 // logic_kernel's shared memory: the env passes' per-car words
@@ -2403,35 +2103,29 @@ __global__ void __launch_bounds__(SBLOCK) debug_car_contact_kernel(const float* 
   }
 }
 __global__ void __launch_bounds__(SBLOCK) car_contact_kernel(Params P) {
-  const int tid = threadIdx.x, C = P.C;
-  const int el = tid / C, car = tid - el * C;
-  const int env = blk_env_of(P, el, wg_block(P) * P.epb + el);
+  const CarSlot s = car_slot(P, wg_block(P));
   if (blk_empty(P, wg_block(P))) return;   // empty workgroup (device-built block map)
-  car_contact_block(P, tid, el, car, env, env >= 0 ? env * C + car : 0, smem);
+  car_contact_block(P, s.tid, s.el, s.car, s.env, s.n, smem);
 }
 
 __global__ void __launch_bounds__(SBLOCK) logic_kernel(Params P, float* obs, float* reward, uint8_t* car_flags,
                                                       uint8_t* env_flags, int auto_reset, float* terminal_obs) {
   __shared__ LogicLDS L;
   __shared__ TrackLDS TL;
-  const int tid = threadIdx.x, C = P.C;
-  const int el = tid / C, car = tid - el * C;
-  const int slot = wg_block(P) * P.epb + el;
-  const int env = blk_env_of(P, el, slot);
-  const int n = env >= 0 ? env * C + car : 0;
+  const CarSlot s = car_slot(P, wg_block(P));
   if (blk_empty(P, wg_block(P))) return;   // empty workgroup (device-built block map)
   PROF_B0(P.blk0);
   LPROF(0);
   Car c;
   double sim;
   int pend_in, reason_in;
-  logic_load(P, env, car, n, c, sim, pend_in, reason_in);   // state loads issued before the staging barrier
+  logic_load(P, s.env, s.car, s.n, c, sim, pend_in, reason_in);   // state loads issued before the staging barrier
   TrackDev T = P.tracks[blk_track_of(P, wg_block(P))];
-  stage_track_lds(T, TL, tid);
+  stage_track_lds(T, TL, s.tid);
   __syncthreads();
   T.segs = TL.segs; T.prefix = TL.prefix;
-  logic_run(P, T, TL, L, tid, el, car, env, n, c, sim, pend_in, reason_in, obs, reward, car_flags, env_flags, auto_reset,
-            terminal_obs);
+  logic_run(P, T, TL, L, s.tid, s.el, s.car, s.env, s.n, c, sim, pend_in, reason_in, obs, reward, car_flags, env_flags,
+            auto_reset, terminal_obs);
 }
 
 // model_kernel + logic_kernel in one launch (NASCAR_FUSE_ML / nascar_set_fused_logic): each block runs its envs'
@@ -2460,23 +2154,19 @@ static __device__ void fused_logic_phase(const Params& P, int tid, int el, int c
 __device__ __forceinline__ void model_logic_body(const Params& P, const void* actions, int discrete, int want_term, int policy,
                                                  uint64_t seed, int64_t step, const float* pobs, float* obs, float* reward,
                                                  uint8_t* car_flags, uint8_t* env_flags, int auto_reset, float* terminal_obs) {
-  const int tid = threadIdx.x, C = P.C;
-  const int el = tid / C, car = tid - el * C;
-  const int slot = wg_block(P) * P.epb + el;
-  const int env = blk_env_of(P, el, slot);
-  const int n = env >= 0 ? env * C + car : 0;
+  const CarSlot s = car_slot(P, wg_block(P));
   if (blk_empty(P, wg_block(P))) return;   // empty workgroup (device-built block map)
   Car c;
   SegReg sr;
   double sim;
   int pend_in, reason_in;
-  logic_load_env(P, env, car, sim, pend_in, reason_in);
-  model_block<true>(P, actions, discrete, want_term, policy, seed, step, pobs, tid, env, n, c, sr);
+  logic_load_env(P, s.env, s.car, sim, pend_in, reason_in);
+  model_block<true>(P, actions, discrete, want_term, policy, seed, step, pobs, s.tid, s.env, s.n, c, sr);
   __syncthreads();   // the block's Box2D steps done: body state stored, contact slots written back (LDS free)
   PROF(6);           // profile builds: the fused kernel's logic half (stamp slots 6-9)
-  if (P.car_contact) car_contact_block(P, tid, el, car, env, n, smem);   // block-uniform; holds its own barriers
-  fused_logic_phase(P, tid, el, car, env, n, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, c, sim, pend_in,
-                    reason_in, sr);
+  if (P.car_contact) car_contact_block(P, s.tid, s.el, s.car, s.env, s.n, smem);   // block-uniform; holds its own barriers
+  fused_logic_phase(P, s.tid, s.el, s.car, s.env, s.n, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, c, sim,
+                    pend_in, reason_in, sr);
   PROF(8);
   PROF_RT(9);
 }
@@ -2506,15 +2196,7 @@ typedef const __attribute__((address_space(4))) Params* ParamsK;
 __shared__ TrackLDS g_ro_track;    // rollout_kernel: the block's track segments
 __shared__ LogicLDS g_ro_logic;    // rollout_kernel: logic_run's env reductions / obs rows
 
-struct RoSlot { int tid, el, car, env, n; };
-__device__ __forceinline__ RoSlot ro_slot(const Params& P) {
-  RoSlot r;
-  r.tid = threadIdx.x;
-  r.el = r.tid / P.C; r.car = r.tid - r.el * P.C;
-  r.env = blk_env_of(P, r.el, blockIdx.x * P.epb + r.el);
-  r.n = r.env >= 0 ? r.env * P.C + r.car : 0;
-  return r;
-}
+__device__ __forceinline__ CarSlot ro_slot(const Params& P) { return car_slot(P, blockIdx.x); }
 __device__ __forceinline__ TrackDev ro_track(const Params& P) {
   TrackDev T = P.tracks[blk_track_of(P, blockIdx.x)];
   T.segs = g_ro_track.segs; T.prefix = g_ro_track.prefix;
@@ -2523,7 +2205,7 @@ __device__ __forceinline__ TrackDev ro_track(const Params& P) {
 static __device__ __attribute__((noinline)) void ro_model_phase(ParamsK Pk, int policy, uint64_t seed, int64_t step,
                                                                 const float* obs) {
   const Params& P = *(const Params*)Pk;
-  const RoSlot s = ro_slot(P);
+  const CarSlot s = ro_slot(P);
   if (s.env < 0) return;
   const TrackDev T = ro_track(P);
   Car c;
@@ -2536,7 +2218,7 @@ static __device__ __attribute__((noinline)) void ro_model_phase(ParamsK Pk, int 
 static __device__ __attribute__((noinline)) void ro_logic_phase(ParamsK Pk, float* obs, float* reward, uint8_t* car_flags,
                                                                 uint8_t* env_flags, int auto_reset) {
   const Params& P = *(const Params*)Pk;
-  const RoSlot s = ro_slot(P);
+  const CarSlot s = ro_slot(P);
   const TrackDev T = ro_track(P);
   Car c;
   double sim;
@@ -2547,7 +2229,7 @@ static __device__ __attribute__((noinline)) void ro_logic_phase(ParamsK Pk, floa
 }
 static __device__ __attribute__((noinline)) void ro_contact_phase(ParamsK Pk) {
   const Params& P = *(const Params*)Pk;
-  const RoSlot s = ro_slot(P);
+  const CarSlot s = ro_slot(P);
   const TrackDev T = P.tracks[blk_track_of(P, blockIdx.x)];   // the scratch follows the staged sensor wall image
   car_contact_block(P, s.tid, s.el, s.car, s.env, s.n, smem + ((2 * (size_t)T.nwall * sizeof(float4) + 15) & ~(size_t)15));
 }
@@ -2786,16 +2468,14 @@ pipe_sensor_kernel(const Params* __restrict__ Pg, PipeDev Q, float* obs, int pas
 }
 
 __global__ void __launch_bounds__(SBLOCK) reset_kernel(Params P, const uint8_t* mask, float* obs) {
-  const int tid = threadIdx.x, C = P.C;
-  const int el = tid / C, car = tid - el * C;
-  const int slot = blockIdx.x * P.epb + el;
-  int env = blk_env_of(P, el, slot);
+  const CarSlot s = car_slot(P, blockIdx.x);
+  int env = s.env;   // -1 too for an env the mask leaves as it is
   if (blk_empty(P, blockIdx.x)) return;   // empty workgroup (device-built block map)
-  if (env >= 0 && mask && !mask[env]) { P.pose[env * C + car] = make_float4(0.f, 0.f, 0.f, __int_as_float(0)); env = -1; }
+  if (env >= 0 && mask && !mask[env]) { P.pose[s.n] = make_float4(0.f, 0.f, 0.f, __int_as_float(0)); env = -1; }
   const TrackDev T = P.tracks[blk_track_of(P, blockIdx.x)];
   const WallSet S{T.walls, T.nwall, T.bp, T.sn, T.wfat};
   if (env >= 0) {
-    const int n = env * C + car;
+    const int n = s.n;
     const bool fresh = P.env_i32[E_CREATED * P.E + env] == 0;
     Car c;
     car_load(P, n, c);
@@ -2807,7 +2487,7 @@ __global__ void __launch_bounds__(SBLOCK) reset_kernel(Params P, const uint8_t* 
     car_store(P, n, c);
   }
   __syncthreads();   // every lane of an env has read E_CREATED before its car 0 writes it
-  if (env >= 0 && car == 0) {
+  if (env >= 0 && s.car == 0) {
     P.env_time[env] = 0.0;
     P.env_i32[E_CREATED * P.E + env] = 1; P.env_i32[E_PENDING * P.E + env] = 0; P.env_i32[E_REASON * P.E + env] = 0;
     P.env_i32[E_TERMINATED * P.E + env] = 0; P.env_i32[E_TRUNCATED * P.E + env] = 0;
@@ -2826,14 +2506,11 @@ __device__ __forceinline__ InfoCore info_core(const WallSet& S, const Car& c) {
   return r;
 }
 __global__ void __launch_bounds__(SBLOCK) info_kernel(Params P, double* info) {
-  const int tid = threadIdx.x, C = P.C;
-  const int el = tid / C, car = tid - el * C;
-  const int slot = blockIdx.x * P.epb + el;
-  const int env = blk_env_of(P, el, slot);
+  const CarSlot s = car_slot(P, blockIdx.x);
+  const int env = s.env, n = s.n;
   if (env < 0 || blk_track_of(P, blockIdx.x) < 0) return;
   const TrackDev T = P.tracks[blk_track_of(P, blockIdx.x)];
   const WallSet S{T.walls, T.nwall, T.bp, T.sn, T.wfat};
-  const int n = env * C + car;
   Car c;
   car_load(P, n, c);
   double* o = info + (size_t)n * N_INFO;
@@ -3676,12 +3353,8 @@ extern "C" int nascar_set_sensor_lanes(NascarHandle* h, int32_t lanes) {
   return 0;
 }
 
-extern "C" int nascar_create(const NascarConfig* cfg, NascarHandle** out) {
-  if (!cfg || !out) return fail("null argument");
-  if (cfg->num_envs < 1) return fail("num_envs must be >= 1");
-  if (cfg->num_cars < 1 || cfg->num_cars > 64) return fail("num_cars must be in [1, 64]");
-  HIPCHK(hipSetDevice(cfg->device));
-  NascarHandle* h = new NascarHandle();
+// nascar_create's work on the new handle; on an error the caller releases whatever is allocated by then
+static int init_handle(NascarHandle* h, const NascarConfig* cfg) {
   h->cfg = *cfg;
   h->E = cfg->num_envs; h->C = cfg->num_cars; h->N = h->E * h->C;
   h->epb = auto_epb(h->E, h->C, cfg->device);
@@ -3711,14 +3384,14 @@ extern "C" int nascar_create(const NascarConfig* cfg, NascarHandle** out) {
   h->off_ctl = o; o = align256(o + sizeof(double) * 4 * N);
   h->arena_bytes = o;
   hipError_t e = hipMalloc(&h->arena, o);
-  if (e != hipSuccess) { delete h; return fail("hipMalloc(%zu) failed: %s", o, hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail("hipMalloc(%zu) failed: %s", o, hipGetErrorString(e));
   hipMemset(h->arena, 0, o);
   h->d_ctl = (double*)((char*)h->arena + h->off_ctl);
   // pose hand-off [2][N] float4, then the per-env reset bytes (Params::reset_env)
   const size_t pose_bytes = sizeof(float4) * 2 * N + ((size_t)E + 15) / 16 * 16;
-  if (hipMalloc(&h->d_pose, pose_bytes) != hipSuccess) { hipFree(h->arena); delete h; return fail("hipMalloc(pose) failed"); }
+  if (hipMalloc(&h->d_pose, pose_bytes) != hipSuccess) return fail("hipMalloc(pose) failed");
   hipMemset(h->d_pose, 0, pose_bytes);
-  if (hipMalloc(&h->d_pose_cs, sizeof(double2) * 2 * N) != hipSuccess) { hipFree(h->arena); hipFree(h->d_pose); delete h; return fail("hipMalloc(pose_cs) failed"); }
+  if (hipMalloc(&h->d_pose_cs, sizeof(double2) * 2 * N) != hipSuccess) return fail("hipMalloc(pose_cs) failed");
   hipMemset(h->d_pose_cs, 0, sizeof(double2) * 2 * N);
   HIPCHK(hipMalloc(&h->d_ray_cs, sizeof(h_ray_cs)));
   HIPCHK(hipMemcpy(h->d_ray_cs, h_ray_cs, sizeof(h_ray_cs), hipMemcpyHostToDevice));
@@ -3730,6 +3403,15 @@ extern "C" int nascar_create(const NascarConfig* cfg, NascarHandle** out) {
     const int nq = q ? atoi(q) : 4;
     h->ro_streams = std::max(1, std::min(nq > 0 ? nq : 4, 4));
   }
+  return 0;
+}
+extern "C" int nascar_create(const NascarConfig* cfg, NascarHandle** out) {
+  if (!cfg || !out) return fail("null argument");
+  if (cfg->num_envs < 1) return fail("num_envs must be >= 1");
+  if (cfg->num_cars < 1 || cfg->num_cars > 64) return fail("num_cars must be in [1, 64]");
+  HIPCHK(hipSetDevice(cfg->device));
+  NascarHandle* h = new NascarHandle();
+  if (init_handle(h, cfg)) { nascar_destroy(h); return -1; }   // (the error text stays: nascar_destroy reports nothing)
   *out = h;
   return 0;
 }
@@ -4290,43 +3972,38 @@ static int sensor_impl() {
 static int ray_lpc(const NascarHandle* h) {
   return h->ray_lanes == 4 ? 4 : 16;   // nascar_set_sensor_lanes / NASCAR_RAY_LPC
 }
+// one ray_sensor_kernel instantiation's launch: nb step-kernel workgroups, each `sub` sensor workgroups of RB threads
+template <int LPC, int RB, bool GW, bool VIS>
+static void launch_ray(int nb, int sub, size_t lds, void* stream, const Params& P, float* obs, float* terminal_obs,
+                       int passes) {
+  hipLaunchKernelGGL((ray_sensor_kernel<LPC, RB, GW, VIS>), dim3(nb * sub), dim3(RB), lds, (hipStream_t)stream, P, obs,
+                     terminal_obs, passes, sub);
+}
 // nb step-kernel workgroups from P.blk0 (each is `sub` sensor workgroups)
 // VIS: the opponent-aware instantiations (nascar_set_car_visibility); false: the kernels as they are without the extension
 template <bool VIS>
 static void launch_sensors_vis(NascarHandle* h, const Params& P, int nb, float* obs, float* terminal_obs, int passes,
                                void* stream, int impl) {
   if (impl == 1) {
-    const size_t rlds = h->max_sensor_lds;   // >= 2 float4 per wall
     const int cars = h->epb * h->C;          // cars per step-kernel workgroup
-    if (ray_lpc(h) == 16) {
-      if (h->sensor_block < BLOCK) {   // 64 / 128 threads: the walls from the global image, no LDS
-        const int rb = h->sensor_block, sub = (cars + rb / 16 - 1) / (rb / 16);
-        if (rb == 64)
-          hipLaunchKernelGGL((ray_sensor_kernel<16, 64, true, VIS>), dim3(nb * sub), dim3(rb), 0, (hipStream_t)stream, P, obs,
-                             terminal_obs, passes, sub);
-        else
-          hipLaunchKernelGGL((ray_sensor_kernel<16, 128, true, VIS>), dim3(nb * sub), dim3(rb), 0, (hipStream_t)stream, P, obs,
-                             terminal_obs, passes, sub);
-        return;
-      }
-      // every sensor workgroup stages the whole wall image: larger workgroups stage it for more cars
-      int rb = h->sensor_block;
-      while (rb > BLOCK && rb / 2 >= cars * 16) rb /= 2;   // no wider than a step workgroup's cars need (small batches)
-      const int sub = (cars + rb / 16 - 1) / (rb / 16);
-      if (rb == 1024)
-        hipLaunchKernelGGL((ray_sensor_kernel<16, 1024, false, VIS>), dim3(nb * sub), dim3(rb), rlds, (hipStream_t)stream, P, obs,
-                           terminal_obs, passes, sub);
-      else if (rb == 512)
-        hipLaunchKernelGGL((ray_sensor_kernel<16, 512, false, VIS>), dim3(nb * sub), dim3(rb), rlds, (hipStream_t)stream, P, obs,
-                           terminal_obs, passes, sub);
-      else
-        hipLaunchKernelGGL((ray_sensor_kernel<16, BLOCK, false, VIS>), dim3(nb * sub), dim3(BLOCK), rlds, (hipStream_t)stream, P, obs,
-                           terminal_obs, passes, sub);
+    // the launch shape: lanes per car, threads per sensor workgroup, its LDS
+    int lpc = 16, rb = h->sensor_block;
+    size_t lds = h->max_sensor_lds;          // >= 2 float4 per wall
+    if (ray_lpc(h) != 16) {
+      lpc = RAY_LPC; rb = BLOCK;
+    } else if (rb < BLOCK) {
+      lds = 0;                               // 64 / 128 threads: the walls from the global image, no LDS
     } else {
-      const int sub = (cars + BLOCK / RAY_LPC - 1) / (BLOCK / RAY_LPC);
-      hipLaunchKernelGGL((ray_sensor_kernel<RAY_LPC, BLOCK, false, VIS>), dim3(nb * sub), dim3(BLOCK), rlds, (hipStream_t)stream, P, obs,
-                         terminal_obs, passes, sub);
+      // every sensor workgroup stages the whole wall image: larger workgroups stage it for more cars
+      while (rb > BLOCK && rb / 2 >= cars * 16) rb /= 2;   // no wider than a step workgroup's cars need (small batches)
     }
+    const int sub = (cars + rb / lpc - 1) / (rb / lpc);
+    if (lpc != 16) launch_ray<RAY_LPC, BLOCK, false, VIS>(nb, sub, lds, stream, P, obs, terminal_obs, passes);
+    else if (rb == 64) launch_ray<16, 64, true, VIS>(nb, sub, lds, stream, P, obs, terminal_obs, passes);
+    else if (rb == 128) launch_ray<16, 128, true, VIS>(nb, sub, lds, stream, P, obs, terminal_obs, passes);
+    else if (rb == 1024) launch_ray<16, 1024, false, VIS>(nb, sub, lds, stream, P, obs, terminal_obs, passes);
+    else if (rb == 512) launch_ray<16, 512, false, VIS>(nb, sub, lds, stream, P, obs, terminal_obs, passes);
+    else launch_ray<16, BLOCK, false, VIS>(nb, sub, lds, stream, P, obs, terminal_obs, passes);
     return;
   }
   const size_t lds = h->max_sensor_groups_lds;
@@ -4544,6 +4221,37 @@ extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed
 static void launch_actor(NascarHandle* h, int n, const float* obs, float* actions, void* stream);
 static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int64_t step, const float* obs, float* act,
                         hipStream_t s);
+// The first n shard streams with their join events, and the fork event, created where missing on the handle's device
+// (whatever is current): a stream and its join event both or neither.  `what` names them in the error.
+static int ensure_shard_streams(NascarHandle* h, int n, const char* what) {
+  if ((int)h->sub_stream.size() >= n && h->ev_fork) return 0;
+  int cur = 0;
+  HIPCHK(hipGetDevice(&cur));
+  if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
+  bool ok = true;
+  while (ok && (int)h->sub_stream.size() < n) {
+    hipStream_t st; hipEvent_t ev;
+    ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
+    if (ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { hipStreamDestroy(st); ok = false; }
+    if (ok) { h->sub_stream.push_back(st); h->ev_join.push_back(ev); }
+  }
+  if (ok && !h->ev_fork) ok = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
+  if (cur != h->cfg.device) hipSetDevice(cur);
+  if (!ok) return fail("creating %s failed", what);
+  return 0;
+}
+// The device copy of P that the rollout kernels read (allocated at first use): a stream-ordered upload when it changed
+static int upload_params(NascarHandle* h, const Params& P, hipStream_t stream) {
+  if (!h->d_params) {
+    HIPCHK(hipMalloc(&h->d_params, sizeof(Params)));
+    memset(&h->params_up, 0, sizeof(Params));
+  }
+  if (!h->params_valid || memcmp(&h->params_up, &P, sizeof(Params)) != 0) {
+    h->params_up = P; h->params_valid = true;
+    HIPCHK(hipMemcpyAsync(h->d_params, &h->params_up, sizeof(Params), hipMemcpyHostToDevice, stream));
+  }
+  return 0;
+}
 static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed, int64_t step0, int32_t steps, float* obs,
                            float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, int32_t traj,
                            hipStream_t stream) {
@@ -4560,21 +4268,7 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
     if (!h->map_identity && !genome) S = 1;   // the genome driver walks its shard's env slots of the block map
     if (!h->d_ro_act) HIPCHK(hipMalloc(&h->d_ro_act, sizeof(float) * 2 * (size_t)h->N));
   }
-  if ((int)h->sub_stream.size() < S - 1 || (S > 1 && !h->ev_fork)) {   // on the handle's device, whatever is current
-    int cur = 0;
-    HIPCHK(hipGetDevice(&cur));
-    if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
-    bool ok = true;
-    while (ok && (int)h->sub_stream.size() < S - 1) {   // a stream and its join event, both or neither
-      hipStream_t st; hipEvent_t ev;
-      ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
-      if (ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { hipStreamDestroy(st); ok = false; }
-      if (ok) { h->sub_stream.push_back(st); h->ev_join.push_back(ev); }
-    }
-    if (ok && !h->ev_fork) ok = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
-    if (cur != h->cfg.device) hipSetDevice(cur);
-    if (!ok) return fail("creating the rollout shard streams failed");
-  }
+  if (S > 1 && ensure_shard_streams(h, S - 1, "the rollout shard streams")) return -1;
   auto shard_stream = [&](int s) { return s == 0 ? stream : h->sub_stream[s - 1]; };
   const Params P0 = make_params(h);
   if (S > 1) {
@@ -4659,30 +4353,9 @@ static int rollout_pipe(NascarHandle* h, int policy, uint64_t seed, int64_t step
     HIPCHK(hipMalloc(&h->d_pipe_sdone, sizeof(unsigned) * nb));
     h->pipe_nb = nb;
   }
-  if (h->sub_stream.empty() || !h->ev_fork) {   // one extra stream (the first shard stream) and its join event
-    int cur = 0;
-    HIPCHK(hipGetDevice(&cur));
-    if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
-    bool ok = true;
-    if (h->sub_stream.empty()) {
-      hipStream_t st; hipEvent_t ev;
-      ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
-      if (ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { hipStreamDestroy(st); ok = false; }
-      if (ok) { h->sub_stream.push_back(st); h->ev_join.push_back(ev); }
-    }
-    if (ok && !h->ev_fork) ok = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
-    if (cur != h->cfg.device) hipSetDevice(cur);
-    if (!ok) return fail("creating the pipelined rollout's sensor stream failed");
-  }
-  const Params P = make_params(h);
-  if (!h->d_params) {
-    HIPCHK(hipMalloc(&h->d_params, sizeof(Params)));
-    memset(&h->params_up, 0, sizeof(Params));
-  }
-  if (!h->params_valid || memcmp(&h->params_up, &P, sizeof(Params)) != 0) {   // stream-ordered upload when changed
-    h->params_up = P; h->params_valid = true;
-    HIPCHK(hipMemcpyAsync(h->d_params, &h->params_up, sizeof(Params), hipMemcpyHostToDevice, stream));
-  }
+  // one extra stream (the first shard stream) and its join event
+  if (ensure_shard_streams(h, 1, "the pipelined rollout's sensor stream")) return -1;
+  if (upload_params(h, make_params(h), stream)) return -1;
   hipStream_t ss = h->sub_stream[0];
   const size_t NC = (size_t)h->N, E = (size_t)h->E;
   for (int k0 = 0; k0 < steps; k0 += (int)chunk) {
@@ -4775,15 +4448,8 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
   if (h->ro_streams > 0)
     return rollout_sharded(h, h->ro_streams, policy, seed, step0, steps, obs, reward, car_flags, env_flags, auto_reset,
                            traj, (hipStream_t)stream);
-  Params P = make_params(h);   // ro_streams == 0: the fused rollout_kernel
-  if (!h->d_params) {
-    HIPCHK(hipMalloc(&h->d_params, sizeof(Params)));
-    memset(&h->params_up, 0, sizeof(Params));
-  }
-  if (!h->params_valid || memcmp(&h->params_up, &P, sizeof(Params)) != 0) {   // stream-ordered upload when changed
-    h->params_up = P; h->params_valid = true;
-    HIPCHK(hipMemcpyAsync(h->d_params, &h->params_up, sizeof(Params), hipMemcpyHostToDevice, (hipStream_t)stream));
-  }
+  // ro_streams == 0: the fused rollout_kernel
+  if (upload_params(h, make_params(h), (hipStream_t)stream)) return -1;
   // >= 2 float4 per wall of the largest track; the car-car extension's scratch after it
   const size_t lds = ((h->max_sensor_lds + 15) & ~(size_t)15) + (h->car_contact ? CC_LDS_BYTES : 0);
   hipLaunchKernelGGL(rollout_kernel, dim3(h->nblocks), dim3(SBLOCK), lds, (hipStream_t)stream, (const Params*)h->d_params,
