@@ -122,8 +122,8 @@ int nascar_step(NascarHandle* h, const void* actions, int32_t discrete, float* o
 /* nascar_step with the actions of device action source `policy` (0, 1, 3: see nascar_policy_actions) computed on
  * the current obs inside the step launch -- one closed-loop driver step (game/control drivers' loop) without a
  * separate action launch; identical results to nascar_policy_actions(policy, seed, step) + nascar_step.  Policies 2
- * and 4 (the MLP controllers) and 5 (the genome drivers) are not available here: use nascar_policy_actions +
- * nascar_step, or nascar_rollout. */
+ * and 4 (the MLP controllers), 5 (the genome drivers) and 6 (the sampled actor-critic) are not available here: use
+ * nascar_policy_actions + nascar_step, or nascar_rollout (policy 6: nascar_collect). */
 int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, float* obs, float* reward,
                        uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs, void* stream);
 
@@ -283,7 +283,11 @@ int nascar_set_state(NascarHandle* h, const void* src_device, void* stream);
  *             however many controllers are loaded.  Fails without a table.  actions 8-byte aligned.
  *   policy 5: the genome driver -- every car runs BaseController._fallback_control with its constants replaced by the
  *             car's 12 genes (nascar_set_genomes), one launch of its own (genome_policy_kernel); it shares the per-car
- *             control state with policies 1 and 3.  Fails without a genome table. */
+ *             control state with policies 1 and 3.  Fails without a genome table.
+ *   policy 6: the sampled actor-critic of nascar_set_actor_critic -- every car draws a ~ N(mu(obs), exp(log_std)^2)
+ *             from the Gaussian actor and takes min(max(a, -1), 1), the action SB3's collect_rollouts steps the env with;
+ *             the draw is the one of (seed, car, step), see nascar_collect.  Fails without an actor-critic.  actions
+ *             8-byte aligned. */
 int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, const float* obs,
                           float* actions, void* stream);
 
@@ -323,7 +327,13 @@ int nascar_actor_forward(NascarHandle* h, const float* obs, int32_t n, float* ac
  * nascar_check_controller (host only, no device, h not needed): 0 if nascar_add_controller would accept the shape,
  *   activation and output, < 0 with the message otherwise.
  * nascar_add_controller: copies the weights to the device; returns the controller's id >= 0 (at most 16 per handle;
- *   ids stay valid for the handle's life).
+ *   ids stay valid for the handle's life).  Two more kinds serve nascar_set_actor_critic and drive no car of the field
+ *   (nascar_set_car_controllers and nascar_controller_forward refuse them): output 4, the sampled Gaussian actor (w3 / b3
+ *   give the mean), and act_dim 1 with output 3, a critic (w3 [1][h2], b3 [1]: the value head).
+ * nascar_update_controller: same-shape weights into a loaded controller, by an upload ordered on `stream` (launches
+ *   enqueued before it on that stream run the old weights, later ones the new); h1, h2, activation, act_dim and output
+ *   must be the loaded controller's, anything else is an error naming both.  A learner updates its nets every
+ *   iteration, and a handle holds 16 ids.
  * nascar_controller_forward: controller `id` on any device batch, obs [n][38] -> actions [n][2] float32 (actions
  *   8-byte aligned).  256-256 ReLU with output 2 performs the float32 policy-2 kernel's operations in its order: the
  *   results are equal bit for bit.
@@ -336,7 +346,7 @@ int nascar_actor_forward(NascarHandle* h, const float* obs, int32_t n, float* ac
 typedef struct NascarMlp {
     int32_t obs_dim, h1, h2, act_dim;
     int32_t activation;      /* 0 ReLU, 1 Tanh */
-    int32_t output;          /* 0 raw, 1 clip, 2 squash */
+    int32_t output;          /* 0 raw, 1 clip, 2 squash; 3 value (act_dim 1), 4 sampled: nascar_set_actor_critic */
     const float *w1, *b1, *w2, *b2, *w3, *b3;   /* PyTorch layouts, host */
 } NascarMlp;
 #define NASCAR_CTRL_RULE (-1)      /* policy 1 */
@@ -347,6 +357,48 @@ int nascar_check_controller(const NascarMlp* mlp);
 int nascar_add_controller(NascarHandle* h, const NascarMlp* mlp);
 int nascar_controller_forward(NascarHandle* h, int32_t id, const float* obs, int32_t n, float* actions, void* stream);
 int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl);
+int nascar_update_controller(NascarHandle* h, int32_t id, const NascarMlp* mlp, void* stream);
+
+/* On-policy collection: the loop of SB3's on-policy algorithms, as learn/ppo.py:65-107 and learn/a2c.py run it
+ * (OnPolicyAlgorithm.collect_rollouts, then RolloutBuffer.compute_returns_and_advantage), on the device.
+ * nascar_set_actor_critic: the handle's actor-critic -- pi_id a sampled actor (output 4) and vf_id a critic (act_dim 1,
+ *   output 3) from nascar_add_controller, and log_std [2] (host, finite; ActorCriticPolicy's state-independent log_std).
+ *   log_std NULL clears it.  Calling it again with the same ids sets a new log_std (with nascar_update_controller: a
+ *   learner's update).
+ * The draw of car n at (seed, step): with key the counter key of policy 0 (seed, n, step) and mix32 its hash,
+ *     u0 = ((mix32(key ^ 0x5A4D504C45) >> 8) + 1) * 2^-24  in (0, 1]
+ *     u1 = (mix32(key ^ 0x3C6EF372FE94F82B) >> 8) * 2^-24   in [0, 1)
+ *     r = sqrtf(-2 logf(u0)),  eps = (r cosf(2 pi u1), r sinf(2 pi u1))          (Box-Muller, float32)
+ *   a_j = mu_j + expf(log_std_j) * eps_j is the recorded action (unclipped, as SB3's buffer keeps it), min(max(a, -1), 1)
+ *   steps the env, and logp = sum_j (-(a_j - mu_j)^2 / (2 std_j^2) - log_std_j - log sqrt(2 pi)) is
+ *   DiagGaussianDistribution.log_prob.  It depends on (seed, car index, step) alone, never on the shard, tile or lane
+ *   that computes it; the two salts are used by no other action source.
+ * nascar_collect: `steps` x (policy 6 on the current obs + CarEnv.step with auto-reset) as policy 6 of the sharded
+ *   rollout, always with the per-step records and the obs trajectory of nascar_rollout (obs [steps + 1][E*C*38], record 0
+ *   the current observation on entry; reward, car_flags [steps][E*C]; env_flags [steps][E]; none may be NULL), plus
+ *     actions [steps][E*C][2], logp [steps][E*C]   the draws above (actions and obs 8-byte aligned)
+ *     values [steps + 1][E*C]                      the critic on obs record k
+ *     timeout_values [steps][E*C]                  the critic on the TERMINAL observation of step k for the cars of envs
+ *                                                  that were truncated and not terminated there, 0 everywhere else: SB3
+ *                                                  bootstraps a time limit with reward += gamma * V(terminal_observation)
+ *   Identical results to `steps` calls of nascar_policy_actions(6, seed, step0 + k) + nascar_step(auto_reset).  Every car
+ *   slot runs the one actor-critic; actor and critic ride in one launch when they share (h1, h2, activation).  Fails
+ *   with rollout streams 0, under nascar_set_rollout_pipe, with fitness accumulation on and without an actor-critic;
+ *   nascar_step_driven and nascar_rollout refuse policy 6.  Random-track mode and envs that do not sit in one track's
+ *   workgroups in order run as one shard, as policy 4 does.
+ * nascar_gae: generalised advantage estimation over `steps` records of any device buffers of the handle's E x C shape
+ *   (reward, timeout_values, adv, ret [steps][E*C]; values [steps + 1][E*C]; env_flags [steps][E]), float32 throughout in
+ *   the operation order of RolloutBuffer.compute_returns_and_advantage under NumPy 2 promotion:
+ *     r' = reward + g * timeout_value,  g = (float)gamma;   nnt = 1 - (terminated | truncated of the car's env at step k)
+ *     delta = (r' + (g * V[k+1]) * nnt) - V[k];   A[k] = delta + ((float)(gamma * lambda) * nnt) * A[k+1],  A[steps] = 0
+ *     ret[k] = A[k] + V[k]
+ *   reproducible bit for bit (no fused multiply-adds). */
+int nascar_set_actor_critic(NascarHandle* h, int32_t pi_id, int32_t vf_id, const float* log_std);
+int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps, float* obs, float* reward,
+                   uint8_t* car_flags, uint8_t* env_flags, float* actions, float* logp, float* values, float* timeout_values,
+                   void* stream);
+int nascar_gae(NascarHandle* h, const float* reward, const float* values, const float* timeout_values,
+               const uint8_t* env_flags, int32_t steps, double gamma, double lambda, float* adv, float* ret, void* stream);
 
 /* Genome drivers: the rule driver of the reference's genetic trainer (game/control/genetic_controller.py,
  * learn/genetic_trainer.py), one genome per car.  GeneticController.control cannot run as written (its line 81 reads an

@@ -9,7 +9,7 @@ one fused HIP kernel for gfx950 over E envs x C cars (libnascar.so, include/nasc
 from .track import Track, available_tracks, build_walls, load_track, track_path  # noqa: F401
 
 __all__ = ["Track", "available_tracks", "build_walls", "load_track", "track_path", "BatchedCarEnv", "CarEnv",
-           "BaseEnv", "VecCarEnv"]
+           "BaseEnv", "VecCarEnv", "RolloutBatch", "ActorCriticNet"]
 
 
 def __getattr__(name):   # torch-dependent pieces load lazily
@@ -22,4 +22,7 @@ def __getattr__(name):   # torch-dependent pieces load lazily
     if name == "VecCarEnv":
         from .vec_env import VecCarEnv
         return VecCarEnv
+    if name in ("RolloutBatch", "ActorCriticNet"):
+        from . import onpolicy
+        return getattr(onpolicy, name)
     raise AttributeError(name)

@@ -151,6 +151,14 @@ def lib():
     L.nascar_controller_forward.restype = ctypes.c_int
     L.nascar_set_car_controllers.argtypes = [vp, ctypes.POINTER(i32)]
     L.nascar_set_car_controllers.restype = ctypes.c_int
+    L.nascar_update_controller.argtypes = [vp, i32, ctypes.POINTER(NascarMlp), vp]
+    L.nascar_update_controller.restype = ctypes.c_int
+    L.nascar_set_actor_critic.argtypes = [vp, i32, i32, fp]
+    L.nascar_set_actor_critic.restype = ctypes.c_int
+    L.nascar_collect.argtypes = [vp, u64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.nascar_collect.restype = ctypes.c_int
+    L.nascar_gae.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_double, ctypes.c_double, vp, vp, vp]
+    L.nascar_gae.restype = ctypes.c_int
     L.nascar_set_genomes.argtypes = [vp, d_p, vp]
     L.nascar_set_genomes.restype = ctypes.c_int
     L.nascar_set_fitness.argtypes = [vp, i32, vp]
@@ -200,6 +208,7 @@ EXPORTED = ["nascar_create", "nascar_destroy", "nascar_last_error", "nascar_add_
             "nascar_set_state", "nascar_policy_actions", "nascar_set_step_events", "nascar_set_actor", "nascar_set_actor_precision", "nascar_actor_forward",
             "nascar_check_controller", "nascar_add_controller", "nascar_controller_forward", "nascar_set_car_controllers",
             "nascar_set_genomes", "nascar_set_fitness", "nascar_get_fitness",
+            "nascar_update_controller", "nascar_set_actor_critic", "nascar_collect", "nascar_gae",
             "nascar_debug_sincosf", "nascar_debug_f64math", "nascar_debug_toi", "nascar_debug_collide", "nascar_debug_car_contact", "nascar_debug_sensors", "nascar_track_draw", "nascar_set_random_tracks",
             "nascar_get_env_tracks", "nascar_vec_post", "nascar_check_actions", "nascar_set_track_cache",
             "nascar_prebuild_track", "nascar_debug_block_map"]
@@ -211,14 +220,14 @@ def check(rc):
     return rc
 
 
-def mlp_struct(ctrl):
-    """(NascarMlp, the arrays it points to) for a nascargymnasium_amd.policy.Controller; keep the arrays alive while
-    the struct is in use."""
+def mlp_struct(ctrl, output=None):
+    """(NascarMlp, the arrays it points to) for a nascargymnasium_amd.policy.Controller or ValueNet (act_dim 1, output 3);
+    `output` overrides the controller's.  Keep the arrays alive while the struct is in use."""
     import numpy as np
     arrs = [np.ascontiguousarray(a, np.float32) for a in ctrl.arrays]
     fp = ctypes.POINTER(ctypes.c_float)
-    m = NascarMlp(38, int(ctrl.h1), int(ctrl.h2), 2, int(ctrl.activation), int(ctrl.output),
-                  *[a.ctypes.data_as(fp) for a in arrs])
+    m = NascarMlp(38, int(ctrl.h1), int(ctrl.h2), int(arrs[4].shape[0]), int(ctrl.activation),
+                  int(ctrl.output if output is None else output), *[a.ctypes.data_as(fp) for a in arrs])
     return m, arrs
 
 

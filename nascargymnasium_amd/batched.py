@@ -499,10 +499,93 @@ class BatchedCarEnv:
             _lib.check(self.L.nascar_get_fitness(self.h, _ptr(out), _stream()))
         return out
 
+    # ------------------------------------------------------------------ on-policy collection (policy 6)
+    def set_actor_critic(self, ac):
+        """Load a nascargymnasium_amd.policy.ActorCritic (load_sb3_actor_critic for the reference's PPO / A2C checkpoints,
+        random_actor_critic, ActorCriticNet.export) as the handle's sampled actor-critic: policy 6 of policy_actions, and
+        what `collect` runs.  Takes two of the handle's 16 controller ids; `update_actor_critic` replaces the weights
+        without taking more."""
+        from .policy import OUT_SAMPLE
+        mp, _kp = _lib.mlp_struct(ac.pi, OUT_SAMPLE)
+        mv, _kv = _lib.mlp_struct(ac.vf)
+        with torch.cuda.device(self.device):
+            pi_id = _lib.check(self.L.nascar_add_controller(self.h, ctypes.byref(mp)))
+            vf_id = _lib.check(self.L.nascar_add_controller(self.h, ctypes.byref(mv)))
+        ls = np.ascontiguousarray(ac.log_std, np.float32)
+        _lib.check(self.L.nascar_set_actor_critic(self.h, pi_id, vf_id, ls.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        self._ac_ids = (pi_id, vf_id)
+
+    def update_actor_critic(self, ac):
+        """New weights and log_std of the same shapes and activations into the loaded actor-critic, ordered on the
+        current stream: a learner's per-iteration update.  Another shape or activation raises."""
+        from .policy import OUT_SAMPLE
+        if getattr(self, "_ac_ids", None) is None:
+            raise RuntimeError("update_actor_critic: no actor-critic loaded (set_actor_critic first)")
+        mp, _kp = _lib.mlp_struct(ac.pi, OUT_SAMPLE)
+        mv, _kv = _lib.mlp_struct(ac.vf)
+        ls = np.ascontiguousarray(ac.log_std, np.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.nascar_update_controller(self.h, self._ac_ids[0], ctypes.byref(mp), _stream()))
+            _lib.check(self.L.nascar_update_controller(self.h, self._ac_ids[1], ctypes.byref(mv), _stream()))
+        _lib.check(self.L.nascar_set_actor_critic(self.h, self._ac_ids[0], self._ac_ids[1],
+                                                  ls.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+
+    def collect(self, steps: int, seed: int = 0, step0: int = 0, gamma: float = 0.99, gae_lambda: float = 0.95, out=None):
+        """One on-policy rollout of `steps` steps on the device, SB3's OnPolicyAlgorithm.collect_rollouts followed by
+        RolloutBuffer.compute_returns_and_advantage: per step the loaded actor-critic samples a ~ N(mu(obs), exp(log_std)),
+        records a, its log-probability and V(obs), and clip(a, -1, 1) steps the envs with auto-reset; envs that a time
+        limit cut (truncated, not terminated) record V(terminal obs) for the reward bootstrap.  Runs on the sharded
+        rollout's streams; equals `steps` x (policy_actions(6, seed, step0 + k) + step(auto_reset=True)).  Returns a
+        nascargymnasium_amd.onpolicy.RolloutBatch; `out`: a RolloutBatch of caller-owned buffers with at least `steps`
+        records (steps + 1 of obs and values) to write into."""
+        from .onpolicy import RolloutBatch
+        K = int(steps)
+        if K < 1:
+            raise ValueError("collect needs steps >= 1")
+        E, C = self.E, self.C
+        spec = RolloutBatch.spec(E, C)
+        if out is None:
+            out = RolloutBatch(*[torch.empty((K + extra, *inner), dtype=dt, device=self.device)
+                                 for _name, dt, inner, extra in spec])
+        else:
+            for (name, dt, inner, extra), t in zip(spec, out):
+                self._check_record_buffer(name, t, dt, inner, K + extra)
+        with torch.cuda.device(self.device):
+            out.obs[0].copy_(self.obs)
+            _lib.check(self.L.nascar_collect(self.h, int(seed), int(step0), K, _ptr(out.obs), _ptr(out.rewards),
+                                             _ptr(out.car_flags), _ptr(out.env_flags), _ptr(out.actions),
+                                             _ptr(out.log_probs), _ptr(out.values), _ptr(out.timeout_values), _stream()))
+            _lib.check(self.L.nascar_gae(self.h, _ptr(out.rewards), _ptr(out.values), _ptr(out.timeout_values),
+                                         _ptr(out.env_flags), K, float(gamma), float(gae_lambda), _ptr(out.advantages),
+                                         _ptr(out.returns), _stream()))
+            self.reward.copy_(out.rewards[K - 1]); self.car_flags.copy_(out.car_flags[K - 1])
+            self.env_flags.copy_(out.env_flags[K - 1]); self.obs.copy_(out.obs[K])
+        if any(t.shape[0] != K + extra for (_n, _d, _i, extra), t in zip(spec, out)):   # larger caller buffers: this call's records
+            out = RolloutBatch(*[t[:K + extra] for (_n, _d, _i, extra), t in zip(spec, out)])
+        return out
+
+    def gae(self, rewards, values, timeout_values, env_flags, gamma: float = 0.99, gae_lambda: float = 0.95):
+        """(advantages, returns) [K, E, C] of SB3's RolloutBuffer.compute_returns_and_advantage, float32 in its operation
+        order (gae_kernel): rewards [K, E, C] (raw; gamma * timeout_values is added here), values [K + 1, E, C],
+        timeout_values [K, E, C], env_flags [K, E] uint8 (done = terminated | truncated)."""
+        K = int(rewards.shape[0])
+        for name, t, dt, inner, n in (("rewards", rewards, torch.float32, (self.E, self.C), K),
+                                      ("values", values, torch.float32, (self.E, self.C), K + 1),
+                                      ("timeout_values", timeout_values, torch.float32, (self.E, self.C), K),
+                                      ("env_flags", env_flags, torch.uint8, (self.E,), K)):
+            self._check_record_buffer(name, t, dt, inner, n)
+        adv = torch.empty(K, self.E, self.C, dtype=torch.float32, device=self.device)
+        ret = torch.empty_like(adv)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.nascar_gae(self.h, _ptr(rewards), _ptr(values), _ptr(timeout_values), _ptr(env_flags), K,
+                                         float(gamma), float(gae_lambda), _ptr(adv), _ptr(ret), _stream()))
+        return adv, ret
+
     def policy_actions(self, policy: int, seed: int = 0, step: int = 0, obs: Optional[torch.Tensor] = None):
         """device-generated actions: 0 uniform U[-1,1]^2, 1 BaseController fallback driver, 2 the SAC actor, 3 the noisy
         rule driver, 4 the field of per-car controllers (set_car_controllers), 5 the genome drivers (set_genomes: the
-        rule driver with per-car evolved constants; shares the rule driver's per-car state)."""
+        rule driver with per-car evolved constants; shares the rule driver's per-car state), 6 the sampled actor-critic
+        (set_actor_critic): clip(a, -1, 1) of the draw a ~ N(mu(obs), exp(log_std)) of (seed, car, step)."""
         o = self.obs if obs is None else obs
         with torch.cuda.device(self.device):
             _lib.check(self.L.nascar_policy_actions(self.h, int(policy), int(seed), int(step), _ptr(o),

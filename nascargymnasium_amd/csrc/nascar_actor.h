@@ -327,6 +327,9 @@ actor_mfma32_kernel(int N, const float* __restrict__ obs, float* __restrict__ ac
 //   output      MLP_OUT_RAW    mu = W3 h + b3
 //               MLP_OUT_CLIP   min(max(mu, -1), 1): SB3 predict for an unsquashed Box policy (PPO, A2C)
 //               MLP_OUT_SQUASH tanh(mu), then unscale_action for the Box(-1, 1) (SAC; actor_mfma32_kernel's expression)
+//               MLP_OUT_VALUE  a critic: w3 is the value head padded to [2][h2] (second row zero); m0 + b3[0] goes to
+//                              values[row] (4-byte stores), nothing to act
+//               MLP_OUT_SAMPLE the Gaussian actor of SB3's on-policy algorithms, sampled: see mlp_sample below
 // Shapes: obs_dim 38 and act_dim 2; (h1, h2) one of MLP_SHAPES below -- 256-256 (the SAC checkpoints), 64-64 (ppo_789,
 // ppo_849), 256-128 (a2c_best_model3), and 128-128, 256-32, 32-256 for other nets; every other shape is rejected when the
 // controller is loaded (mlp_shape_ok), with a message naming it.  That includes TD3's SB3 default [400, 300]: no multiple
@@ -346,7 +349,7 @@ actor_mfma32_kernel(int N, const float* __restrict__ obs, float* __restrict__ ac
 #define MLP_MAX_CTRL 16    // controllers per handle
 #define MLP_MAX_CARS 64    // car slots per env (nascar_create's limit)
 enum { MLP_RELU = 0, MLP_TANH = 1 };
-enum { MLP_OUT_RAW = 0, MLP_OUT_CLIP = 1, MLP_OUT_SQUASH = 2 };
+enum { MLP_OUT_RAW = 0, MLP_OUT_CLIP = 1, MLP_OUT_SQUASH = 2, MLP_OUT_VALUE = 3, MLP_OUT_SAMPLE = 4 };
 #define MLP_SHAPES(X) X(8, 8) X(8, 4) X(8, 1) X(4, 4) X(2, 2) X(1, 8)
 struct MlpDev {        // one loaded controller (device pointers)
   const float* w1t;    // [38][h1]  W1 transposed
@@ -363,7 +366,48 @@ struct MlpLaunch {
   float* act;                  // [E][C][2]
   int env0, nenv, C;
   int slot_id[MLP_MAX_CARS];   // blockIdx.y -> car slot c | controller id << 8
+  // the on-policy outputs (nascar_collect, policy 6); rows are indexed like act, by car
+  float* values;               // MLP_OUT_VALUE: [E][C]
+  float* actions;              // MLP_OUT_SAMPLE: the unclipped action [E][C][2] (null: not kept)
+  float* logp;                 // MLP_OUT_SAMPLE: [E][C] (null: not kept)
+  const uint8_t* tflags;       // non-null: env_flags [E] of the step; only the cars of truncated, not terminated envs
+  int tcars;                   //   are computed (env = car / tcars), and a tile or workgroup without one returns at once
+  float log_std[2];
+  uint64_t seed;
+  int64_t step;
 };
+__device__ __forceinline__ uint32_t mix32(uint64_t x) {   // splitmix64 finaliser
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return (uint32_t)(x >> 32);
+}
+// the counter key of car n at (seed, step): every device action source hashes it, each with salts of its own
+__device__ __forceinline__ uint64_t policy_key(uint64_t seed, int64_t step, size_t n) {
+  return (seed * 0x100000001B3ull) ^ ((uint64_t)n << 24) ^ (uint64_t)step * 0x9E3779B1ull;
+}
+// MLP_OUT_SAMPLE: a ~ N(mu, diag(exp(log_std))^2) as SB3's DiagGaussianDistribution samples and scores it, the noise a
+// Box-Muller pair of two mix32 draws on the car's key (salts SAMPLE_SALT0 / SAMPLE_SALT1, include/nascar.h): u0 in (0, 1],
+// u1 in [0, 1).  The draw depends on (seed, car, step) alone -- not on the shard, tile or lane that computes it.
+// a is what the rollout buffer keeps (unclipped), clip(a, -1, 1) what drives the env (OnPolicyAlgorithm.collect_rollouts),
+// logp = sum_j (-(a_j - mu_j)^2 / (2 std_j^2) - log_std_j - log(sqrt(2 pi))) as torch's Normal.log_prob writes it.
+#define SAMPLE_SALT0 0x5A4D504C45ull
+#define SAMPLE_SALT1 0x3C6EF372FE94F82Bull
+#define HALF_LOG_2PI 0.918938533204672742f
+__device__ __forceinline__ void mlp_sample(const MlpLaunch& L, size_t car, float mu0, float mu1, f32x2& a, float& logp) {
+  const uint64_t key = policy_key(L.seed, L.step, car);
+  const float u0 = (float)((mix32(key ^ SAMPLE_SALT0) >> 8) + 1u) * (1.0f / 16777216.0f);
+  const float u1 = (float)(mix32(key ^ SAMPLE_SALT1) >> 8) * (1.0f / 16777216.0f);
+  const float r = sqrtf(-2.0f * logf(u0)), th = 6.283185307179586f * u1;
+  const float e0 = r * cosf(th), e1 = r * sinf(th);
+  const float s0 = expf(L.log_std[0]), s1 = expf(L.log_std[1]);
+  a = (f32x2){mu0 + s0 * e0, mu1 + s1 * e1};
+  const float d0 = a.x - mu0, d1 = a.y - mu1;
+  const float l0 = (-(d0 * d0) / (2.0f * (s0 * s0)) - L.log_std[0]) - HALF_LOG_2PI;
+  const float l1 = (-(d1 * d1) / (2.0f * (s1 * s1)) - L.log_std[1]) - HALF_LOG_2PI;
+  logp = l0 + l1;
+}
 // tanhf as a call: inlined, its divergent branch (small / large |x|) cuts the unrolled activation loops into 16 (T1 + T2)
 // blocks, the accumulators are copied out of the AGPRs wholesale and the 256-wide nets spill (52 dwords at <8, 8>, 134
 // VGPRs at <2, 2>); called, <2, 2> holds 54 VGPRs + 32 AGPRs (5 waves per SIMD) and nothing spills
@@ -384,6 +428,16 @@ __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
   constexpr int H1 = 32 * T1, H2 = 32 * T2;
   __shared__ float s_b1[H1], s_b2[H2], s_w3[2 * H2];
   const int c = L.slot_id[blockIdx.y] & 255;
+  bool wanted = true;
+  if (L.tflags) {   // timeout values: only the cars of envs that were truncated and not terminated at this step
+    const int it = (blockIdx.x * AM_WAVES + (threadIdx.x >> 6)) * 32 + (threadIdx.x & 31);
+    wanted = false;
+    if (it < L.nenv) {
+      const uint8_t f = L.tflags[((size_t)(L.env0 + it) * L.C + c) / L.tcars];
+      wanted = (f & 2) && !(f & 1);
+    }
+    if (!__syncthreads_or(wanted)) return;   // block-uniform: nothing has been loaded yet
+  }
   const MlpDev W = L.table[L.slot_id[blockIdx.y] >> 8];
   for (int i = threadIdx.x; i < H1; i += 64 * AM_WAVES) s_b1[i] = W.b1[i];
   for (int i = threadIdx.x; i < H2; i += 64 * AM_WAVES) s_b2[i] = W.b2[i];
@@ -393,6 +447,7 @@ __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
   const int tile = blockIdx.x * AM_WAVES + (threadIdx.x >> 6);
   const int i0 = tile * 32;
   if (i0 >= L.nenv) return;
+  if (L.tflags && !__any(wanted)) return;   // wave-uniform
   const int i = i0 + r;
   const size_t car = (size_t)(L.env0 + (i < L.nenv ? i : L.nenv - 1)) * L.C + c;
   const float* xr = L.obs + car * ACT_OBS;
@@ -443,10 +498,52 @@ __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
     const float mu0 = m0 + W.b3[0], mu1 = m1 + W.b3[1];
     f32x2* out = (f32x2*)&L.act[2 * car];
     switch (W.output) {   // wave-uniform
+      case MLP_OUT_VALUE:
+        if (wanted) L.values[car] = mu0;
+        break;
+      case MLP_OUT_SAMPLE: {
+        f32x2 a; float lp;
+        mlp_sample(L, car, mu0, mu1, a, lp);
+        if (L.actions) *(f32x2*)&L.actions[2 * car] = a;
+        if (L.logp) L.logp[car] = lp;
+        *out = mlp_out<MLP_OUT_CLIP>(a.x, a.y);
+        break;
+      }
       case MLP_OUT_SQUASH: *out = mlp_out<MLP_OUT_SQUASH>(mu0, mu1); break;
       case MLP_OUT_CLIP: *out = mlp_out<MLP_OUT_CLIP>(mu0, mu1); break;
       default: *out = mlp_out<MLP_OUT_RAW>(mu0, mu1); break;
     }
+  }
+}
+
+// ------------------------------------------------------------------ GAE (nascar_gae, nascar_collect)
+// Generalised advantage estimation over K records of N = E * C cars, one lane per car walking the records backwards
+// (every load and store coalesced across cars), float32 throughout in the operation order of SB3's
+// RolloutBuffer.compute_returns_and_advantage under NumPy 2 promotion (float32 arrays, Python-float gamma / lambda):
+//   r' = reward + g * tv               g = (float)gamma; tv the time-limit bootstrap V(terminal obs), 0 elsewhere
+//   nnt = 1 - done[k]                  done = terminated | truncated of the car's env (episode_starts[k + 1] == dones[k])
+//   delta = (r' + (g * V[k+1]) * nnt) - V[k]
+//   A[k] = delta + (gl * nnt) * A[k+1] gl = (float)((double)gamma * (double)lambda), A[K] = 0
+//   returns[k] = A[k] + V[k]
+// Built with -ffp-contract=off: no product is fused into a sum, so the result is reproducible bit for bit.
+__global__ void __launch_bounds__(256) gae_kernel(int N, int C, int K, const float* __restrict__ reward,
+                                                  const float* __restrict__ values, const float* __restrict__ tv,
+                                                  const uint8_t* __restrict__ env_flags, float g, float gl,
+                                                  float* __restrict__ adv, float* __restrict__ ret) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const int E = N / C, env = n / C;
+  float a = 0.0f, vnext = values[(size_t)K * N + n];
+  for (int k = K - 1; k >= 0; --k) {
+    const size_t at = (size_t)k * N + n;
+    const float v = values[at];
+    const float rp = reward[at] + g * tv[at];
+    const float nnt = 1.0f - ((env_flags[(size_t)k * E + env] & 3) ? 1.0f : 0.0f);
+    const float delta = (rp + (g * vnext) * nnt) - v;
+    a = delta + (gl * nnt) * a;
+    adv[at] = a;
+    ret[at] = a + v;
+    vnext = v;
   }
 }
 

@@ -1440,13 +1440,7 @@ ray_sensor_kernel(Params P, float* obs, float* terminal_obs, int passes, int SUB
   PROFR(7); PROFR_RT(15);
 }
 
-__device__ __forceinline__ uint32_t mix32(uint64_t x) {   // splitmix64 finaliser
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return (uint32_t)(x >> 32);
-}
+// mix32 (the splitmix64 finaliser) and policy_key: nascar_actor.h, shared with the sampled actor
 // Noisy rule driver (policy 3): with probability NOISE_P16 / 65536 per car-step the driver's action is
 // replaced by the uniform draw of policy 0 (the driver state still advances), as gen_golden.py's
 // "rule_noisy" mode does with a host RNG; cars of one env therefore leave the common start trajectory.
@@ -1455,7 +1449,7 @@ __device__ __forceinline__ uint32_t mix32(uint64_t x) {   // splitmix64 finalise
 // actor_kernel): writes (throttle_brake, steering) to a0, a1
 __device__ __forceinline__ void policy_car(int policy, uint64_t seed, int64_t step, int n, const float* obs, double* ctl,
                                            float& a0, float& a1) {
-  const uint64_t key = (seed * 0x100000001B3ull) ^ ((uint64_t)n << 24) ^ (uint64_t)step * 0x9E3779B1ull;
+  const uint64_t key = policy_key(seed, step, (size_t)n);
   const float u0 = (float)(mix32(key) >> 8) * (2.0f / 16777216.0f) - 1.0f;
   const float u1 = (float)(mix32(key ^ 0xABCDEF12345ull) >> 8) * (2.0f / 16777216.0f) - 1.0f;
   if (policy == 0) { a0 = u0; a1 = u1; return; }
@@ -3257,6 +3251,12 @@ struct NascarHandle {
   MlpDev* d_ctrl = nullptr;
   bool field_set = false;
   int field[MLP_MAX_CARS];
+  // the sampled actor-critic (policy 6, nascar_collect): controller ids of the Gaussian actor (output MLP_OUT_SAMPLE) and
+  // the critic (MLP_OUT_VALUE), log_std, the terminal-observation scratch [N][38] of the timeout values, and the pinned
+  // staging of nascar_update_controller's stream-ordered uploads (ev_ctrl: the staging buffer is free again)
+  bool ac_set = false; int ac_pi = -1, ac_vf = -1; float ac_log_std[2] = {0.0f, 0.0f};
+  float* d_term = nullptr;
+  float* h_ctrl_stage = nullptr; size_t ctrl_stage_floats = 0; hipEvent_t ev_ctrl = nullptr;
   // genome drivers (policy 5, NASCAR_CTRL_GENOME): the per-car gene records, outside the state arena; their upload is
   // staged in pinned memory and ordered on the caller's stream (ev_genome: the staging buffer is free again)
   GenomeRec* d_genome = nullptr; bool genome_set = false;
@@ -3434,6 +3434,9 @@ extern "C" void nascar_destroy(NascarHandle* h) {
   hipFree(h->d_ro_act);
   for (void* p : h->ctrl_mem) hipFree(p);
   hipFree(h->d_ctrl);
+  hipFree(h->d_term);
+  if (h->ev_ctrl) { hipEventSynchronize(h->ev_ctrl); hipEventDestroy(h->ev_ctrl); }
+  if (h->h_ctrl_stage) hipHostFree(h->h_ctrl_stage);
   hipFree(h->d_rt);
   if (h->ev_genome) { hipEventSynchronize(h->ev_genome); hipEventDestroy(h->ev_genome); }
   if (h->h_genome) hipHostFree(h->h_genome);
@@ -4202,6 +4205,9 @@ extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed
   if (policy == 5)
     return fail("driven step: policy 5 (genome drivers) runs in a launch of its own -- use nascar_policy_actions + nascar_step "
                 "or nascar_rollout");
+  if (policy == 6)
+    return fail("driven step: policy 6 (the sampled actor-critic) runs in launches of its own -- use nascar_policy_actions + "
+                "nascar_step or nascar_collect");
   if (policy != 0 && policy != 1 && policy != 3) return fail("driven step policy must be 0, 1 or 3 (got %d)", policy);
   return step_impl(h, nullptr, 0, policy, seed, step, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
 }
@@ -4221,6 +4227,11 @@ extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed
 static void launch_actor(NascarHandle* h, int n, const float* obs, float* actions, void* stream);
 static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int64_t step, const float* obs, float* act,
                         hipStream_t s);
+// the buffers of nascar_collect (policy 6 of the sharded rollout): per-step records beside the rollout's own
+struct CollectBufs { float* actions; float* logp; float* values; float* timeout_values; };
+enum { AC_SAMPLE = 1, AC_VALUE = 2 };
+static int launch_ac(NascarHandle* h, int what, int c0, int n, uint64_t seed, int64_t step, const float* obs, float* act,
+                     float* actions, float* logp, float* values, const uint8_t* tflags, hipStream_t s);
 // The first n shard streams with their join events, and the fork event, created where missing on the handle's device
 // (whatever is current): a stream and its join event both or neither.  `what` names them in the error.
 static int ensure_shard_streams(NascarHandle* h, int n, const char* what) {
@@ -4254,13 +4265,15 @@ static int upload_params(NascarHandle* h, const Params& P, hipStream_t stream) {
 }
 static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed, int64_t step0, int32_t steps, float* obs,
                            float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, int32_t traj,
-                           hipStream_t stream) {
+                           hipStream_t stream, const CollectBufs* col = nullptr) {
   S = std::max(1, std::min(S, h->nblocks));
   const bool rt = h->rt_on && auto_reset;
   if (h->rt_on) S = 1;   // random-track mode: the block map changes between steps, so no shard owns a fixed set of envs
   const bool field = policy == 4, genome = policy == 5;
-  const bool actor = policy == 2 || field || genome;   // the actions come from a launch of their own, into d_ro_act
+  const bool actor = policy == 2 || field || genome || col;   // the actions come from a launch of their own, into d_ro_act
   if (actor) {
+    if (col && !h->ac_set) return fail("policy 6 needs an actor-critic (nascar_set_actor_critic)");
+    if (col && !h->d_term) HIPCHK(hipMalloc(&h->d_term, sizeof(float) * 38 * (size_t)h->N));
     if (field && !h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
     if (genome && !h->genome_set) return fail("policy 5 needs a genome table (nascar_set_genomes)");
     if (policy == 2 && !h->d_actor) return fail("policy 2 needs an actor (nascar_set_actor)");
@@ -4277,6 +4290,12 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
   }
   const size_t NC = (size_t)h->N, E = (size_t)h->E;
   const bool obs_traj = (traj & NASCAR_TRAJ_OBS) != 0;   // obs = [steps + 1][N][38]: record 0 in, record k + 1 out
+  // the cars of shard s (contiguous: the block map is the identity, or there is one shard)
+  auto shard_cars = [&](int s, size_t& c0, size_t& c1) {
+    const int b0 = (int)((int64_t)h->nblocks * s / S), b1 = (int)((int64_t)h->nblocks * (s + 1) / S);
+    c0 = S == 1 ? 0 : std::min((size_t)b0 * h->epb, E) * h->C;
+    c1 = S == 1 ? NC : std::min((size_t)b1 * h->epb, E) * h->C;
+  };
   auto enqueue = [&]() -> int {
     for (int k = 0; k < steps; ++k) {
       const size_t ko = traj ? (size_t)k : 0;
@@ -4293,7 +4312,13 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
           if (actor && ph == 0) {
             const size_t c0 = S == 1 ? 0 : (size_t)b0 * h->epb * h->C;
             const size_t c1 = S == 1 ? NC : std::min((size_t)b1 * h->epb, E) * h->C;
-            if (genome) {
+            if (col) {   // a ~ N(mu, std) and V on the step's observation: actions / logp / values [k], clip(a) drives the step
+              size_t a0, a1;
+              shard_cars(s, a0, a1);
+              if (launch_ac(h, AC_SAMPLE | AC_VALUE, (int)a0, (int)(a1 - a0), seed, step0 + k, o_in, h->d_ro_act,
+                            col->actions + 2 * ko * NC, col->logp + ko * NC, col->values + ko * NC, nullptr, shard_stream(s)))
+                return -1;
+            } else if (genome) {
               if (launch_genome(h, P, b0, b1, 0, 0, ~0ull, o_in, h->d_ro_act, shard_stream(s))) return -1;
             } else if (field) {
               if (launch_field(h, (int)(c0 / h->C), (int)((c1 - c0) / h->C), seed, step0 + k, o_in, h->d_ro_act, shard_stream(s)))
@@ -4305,8 +4330,15 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
                                 o_in, o_out, reward + ko * NC,
                                 car_flags ? car_flags + ko * NC : nullptr,
                                 env_flags ? env_flags + ko * E : (rt ? h->d_rt_flags : h->fit_on ? h->d_fit_flags : nullptr),
-                                auto_reset, nullptr, shard_stream(s), 1 << ph, ph == 1))
+                                auto_reset, col ? h->d_term : nullptr, shard_stream(s), 1 << ph, ph == 1))
             return -1;
+          if (col && ph == 2) {   // SB3's time-limit bootstrap: V(terminal obs) for the cars of truncated, not terminated envs
+            size_t a0, a1;
+            shard_cars(s, a0, a1);
+            if (launch_ac(h, AC_VALUE, (int)a0, (int)(a1 - a0), seed, step0 + k, h->d_term, nullptr, nullptr, nullptr,
+                          col->timeout_values + ko * NC, env_flags + ko * E, shard_stream(s)))
+              return -1;
+          }
           if (h->fit_on && ph == 2 &&
               launch_fitness(h, P, b0, b1, reward + ko * NC, env_flags ? env_flags + ko * E : h->d_fit_flags, shard_stream(s)))
             return -1;
@@ -4314,6 +4346,14 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
       }
       if (rt && rt_after_step(h, P0, env_flags ? env_flags + ko * E : h->d_rt_flags, o_out, stream)) return -1;
     }
+    if (col)   // values [steps]: V of the observation after the last step, the bootstrap of the last record
+      for (int s = 0; s < S; ++s) {
+        size_t a0, a1;
+        shard_cars(s, a0, a1);
+        if (launch_ac(h, AC_VALUE, (int)a0, (int)(a1 - a0), seed, step0 + steps, obs + (size_t)steps * NC * 38, nullptr, nullptr,
+                      nullptr, col->values + (size_t)steps * NC, nullptr, shard_stream(s)))
+          return -1;
+      }
     return 0;
   };
   const int rc = enqueue();
@@ -4415,6 +4455,7 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
                               float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, int32_t traj,
                               void* stream) {
   if (!h || !obs || !reward) return fail("null argument");
+  if (policy == 6) return fail("policy 6 (the sampled actor-critic) fills a learner's buffers: use nascar_collect");
   if (policy < 0 || policy > 5) return fail("rollout policy must be 0, 1, 2, 3, 4 or 5 (got %d)", policy);
   if (policy == 2 && h->ro_streams == 0) return fail("the fused rollout kernel has no actor (policy 2): use the sharded rollout");
   if (policy == 4 && h->ro_streams == 0)
@@ -4454,6 +4495,40 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
   const size_t lds = ((h->max_sensor_lds + 15) & ~(size_t)15) + (h->car_contact ? CC_LDS_BYTES : 0);
   hipLaunchKernelGGL(rollout_kernel, dim3(h->nblocks), dim3(SBLOCK), lds, (hipStream_t)stream, (const Params*)h->d_params,
                      steps, policy, seed, step0, obs, reward, car_flags, env_flags, auto_reset, traj);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps, float* obs, float* reward,
+                              uint8_t* car_flags, uint8_t* env_flags, float* actions, float* logp, float* values,
+                              float* timeout_values, void* stream) {
+  if (!h || !obs || !reward || !car_flags || !env_flags || !actions || !logp || !values || !timeout_values)
+    return fail("null argument");
+  if (steps < 1) return fail("collect: steps must be >= 1 (got %d)", steps);
+  if (!h->ac_set) return fail("policy 6 needs an actor-critic (nascar_set_actor_critic)");
+  if (h->ro_streams == 0)
+    return fail("the fused rollout kernel has no actor-critic (policy 6): use the sharded rollout (rollout streams >= 1)");
+  if (h->ro_pipe > 0)
+    return fail("the pipelined rollout has no actor-critic (policy 6): switch it off (nascar_set_rollout_pipe(h, 0))");
+  if (h->fit_on) return fail("collect steps with auto-reset: switch fitness accumulation off (nascar_set_fitness(h, 0))");
+  if (((uintptr_t)obs | (uintptr_t)actions) & 7) return fail("collect obs / actions must be 8-byte aligned");
+  if (vis_refused(h)) return -1;
+  h->pristine = false;
+  if (prepare(h, (hipStream_t)stream)) return -1;
+  // timeout_values is 0 wherever no time limit cut an episode: the value launches write the other records only
+  HIPCHK(hipMemsetAsync(timeout_values, 0, sizeof(float) * (size_t)steps * h->N, (hipStream_t)stream));
+  const CollectBufs col{actions, logp, values, timeout_values};
+  return rollout_sharded(h, h->ro_streams, 6, seed, step0, steps, obs, reward, car_flags, env_flags, 1,
+                         NASCAR_TRAJ_RECORDS | NASCAR_TRAJ_OBS, (hipStream_t)stream, &col);
+}
+extern "C" int nascar_gae(NascarHandle* h, const float* reward, const float* values, const float* timeout_values,
+                          const uint8_t* env_flags, int32_t steps, double gamma, double lambda, float* adv, float* ret,
+                          void* stream) {
+  if (!h || !reward || !values || !timeout_values || !env_flags || !adv || !ret) return fail("null argument");
+  if (steps < 0) return fail("gae: steps must be >= 0 (got %d)", steps);
+  if (steps == 0) return 0;
+  hipLaunchKernelGGL(gae_kernel, dim3((h->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->N, h->C, steps, reward, values,
+                     timeout_values, env_flags, (float)gamma, (float)(gamma * lambda), adv, ret);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -4650,8 +4725,13 @@ extern "C" int nascar_get_fitness(NascarHandle* h, double* out, void* stream) {
 extern "C" int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, const float* obs,
                                      float* actions, void* stream) {
   if (!h || !actions) return fail("null argument");
-  if (policy < 0 || policy > 5) return fail("unknown policy %d", policy);
+  if (policy < 0 || policy > 6) return fail("unknown policy %d", policy);
   if (policy >= 1 && !obs) return fail("policy %d needs obs", policy);
+  if (policy == 6) {
+    if (!h->ac_set) return fail("policy 6 needs an actor-critic (nascar_set_actor_critic)");
+    if ((uintptr_t)actions & 7) return fail("actor-critic actions must be 8-byte aligned");
+    return launch_ac(h, AC_SAMPLE, 0, h->N, seed, step, obs, actions, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  }
   if (policy == 5) {
     if (!h->genome_set) return fail("policy 5 needs a genome table (nascar_set_genomes)");
     return launch_genome(h, make_params(h), -1, 0, 0, h->N, ~0ull, obs, actions, (hipStream_t)stream);
@@ -4868,26 +4948,24 @@ static bool mlp_shape_ok(int h1, int h2) {
 }
 extern "C" int nascar_check_controller(const NascarMlp* m) {
   if (!m) return fail("null argument");
-  if (m->obs_dim != ACT_OBS || m->act_dim != ACT_OUT || !mlp_shape_ok(m->h1, m->h2))
+  const bool value = m->act_dim == 1 && m->output == MLP_OUT_VALUE;   // a critic: one output, the value
+  if (m->obs_dim != ACT_OBS || (m->act_dim != ACT_OUT && !value) || !mlp_shape_ok(m->h1, m->h2))
     return fail("controller shape %d -> %d -> %d -> %d unsupported: need obs 38, 2 actions and hidden layers 256-256, 256-128, "
                 "256-32, 128-128, 64-64 or 32-256 (the SB3 checkpoints the reference ships; TD3's [400, 300] is not among them)",
                 m->obs_dim, m->h1, m->h2, m->act_dim);
   if (m->activation != MLP_RELU && m->activation != MLP_TANH)
     return fail("controller activation must be 0 (ReLU) or 1 (Tanh), got %d", m->activation);
-  if (m->output != MLP_OUT_RAW && m->output != MLP_OUT_CLIP && m->output != MLP_OUT_SQUASH)
-    return fail("controller output must be 0 (raw), 1 (clip) or 2 (squash), got %d", m->output);
+  if (m->output == MLP_OUT_VALUE && !value) return fail("controller output 3 (value) needs act_dim 1, got %d", m->act_dim);
+  if (m->output != MLP_OUT_RAW && m->output != MLP_OUT_CLIP && m->output != MLP_OUT_SQUASH && m->output != MLP_OUT_VALUE &&
+      m->output != MLP_OUT_SAMPLE)
+    return fail("controller output must be 0 (raw), 1 (clip), 2 (squash), 3 (value, act_dim 1) or 4 (sampled), got %d", m->output);
   return 0;
 }
-extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
-  if (!h || !m) return fail("null argument");
-  if (nascar_check_controller(m)) return -1;
-  if (!m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3) return fail("null controller weights");
-  if ((int)h->ctrl.size() >= MLP_MAX_CTRL) return fail("at most %d controllers per handle", MLP_MAX_CTRL);
-  const int H1 = m->h1, H2 = m->h2;
-  // one allocation: W1^T [38][h1], b1, W2^T [h1][h2], b2, W3 [2][h2], b3 (the transposes give mlp_field_kernel's A
-  // operands coalesced rows)
-  std::vector<float> f((size_t)ACT_OBS * H1 + H1 + (size_t)H1 * H2 + H2 + 2 * (size_t)H2 + 2);
-  float* p = f.data();
+// A controller's device image in host floats: W1^T [38][h1], b1, W2^T [h1][h2], b2, W3 [2][h2], b3 [2] (the transposes
+// give mlp_field_kernel's A operands coalesced rows); a critic's value head is padded with a zero second row
+static size_t mlp_floats(int H1, int H2) { return (size_t)ACT_OBS * H1 + H1 + (size_t)H1 * H2 + H2 + 2 * (size_t)H2 + 2; }
+static void mlp_pack(const NascarMlp* m, float* p) {
+  const int H1 = m->h1, H2 = m->h2, A = m->act_dim;
   float* w1t = p; p += (size_t)ACT_OBS * H1;
   float* b1 = p; p += H1;
   float* w2t = p; p += (size_t)H1 * H2;
@@ -4898,7 +4976,18 @@ extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
     for (int i = 0; i < ACT_OBS; ++i) w1t[(size_t)i * H1 + o] = m->w1[(size_t)o * ACT_OBS + i];
   for (int o = 0; o < H2; ++o)
     for (int i = 0; i < H1; ++i) w2t[(size_t)i * H2 + o] = m->w2[(size_t)o * H1 + i];
-  memcpy(b1, m->b1, 4 * (size_t)H1); memcpy(b2, m->b2, 4 * (size_t)H2); memcpy(w3, m->w3, 8 * (size_t)H2); memcpy(b3, m->b3, 8);
+  memcpy(b1, m->b1, 4 * (size_t)H1); memcpy(b2, m->b2, 4 * (size_t)H2);
+  memset(w3, 0, 8 * (size_t)H2); b3[0] = b3[1] = 0.0f;
+  memcpy(w3, m->w3, 4 * (size_t)A * H2); memcpy(b3, m->b3, 4 * (size_t)A);
+}
+extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
+  if (!h || !m) return fail("null argument");
+  if (nascar_check_controller(m)) return -1;
+  if (!m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3) return fail("null controller weights");
+  if ((int)h->ctrl.size() >= MLP_MAX_CTRL) return fail("at most %d controllers per handle", MLP_MAX_CTRL);
+  const int H1 = m->h1, H2 = m->h2;
+  std::vector<float> f(mlp_floats(H1, H2));   // one allocation
+  mlp_pack(m, f.data());
   int cur = 0;
   HIPCHK(hipGetDevice(&cur));
   if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
@@ -4910,8 +4999,8 @@ extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
   MlpDev D{};
   if (e == hipSuccess) {
     const float* d32 = (const float*)d;
-    D.w1t = d32 + (w1t - f.data()); D.b1 = d32 + (b1 - f.data()); D.w2t = d32 + (w2t - f.data());
-    D.b2 = d32 + (b2 - f.data()); D.w3 = d32 + (w3 - f.data()); D.b3 = d32 + (b3 - f.data());
+    D.w1t = d32; D.b1 = D.w1t + (size_t)ACT_OBS * H1; D.w2t = D.b1 + H1;
+    D.b2 = D.w2t + (size_t)H1 * H2; D.w3 = D.b2 + H2; D.b3 = D.w3 + 2 * (size_t)H2;
     D.h1 = H1; D.h2 = H2; D.activation = m->activation; D.output = m->output;
     e = hipMemcpy(h->d_ctrl + h->ctrl.size(), &D, sizeof(MlpDev), hipMemcpyHostToDevice);
   }
@@ -4921,9 +5010,61 @@ extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
   h->ctrl_mem.push_back(d);
   return (int)h->ctrl.size() - 1;
 }
+// Same-shape weights into a loaded controller's allocation, ordered on `stream` (pinned staging, as the genome table's):
+// a learner updates its nets every iteration, and a handle holds at most MLP_MAX_CTRL ids
+extern "C" int nascar_update_controller(NascarHandle* h, int32_t id, const NascarMlp* m, void* stream) {
+  if (!h || !m) return fail("null argument");
+  if (id < 0 || id >= (int)h->ctrl.size()) return fail("unknown controller id %d (%d loaded)", id, (int)h->ctrl.size());
+  if (nascar_check_controller(m)) return -1;
+  if (!m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3) return fail("null controller weights");
+  const MlpDev& D = h->ctrl[id];
+  if (m->h1 != D.h1 || m->h2 != D.h2 || m->activation != D.activation || m->output != D.output)
+    return fail("update of controller %d: it is %d-%d, activation %d, output %d; the new weights are %d-%d, activation %d, "
+                "output %d (load another controller for another shape or kind)", id, D.h1, D.h2, D.activation, D.output,
+                m->h1, m->h2, m->activation, m->output);
+  const size_t nf = mlp_floats(D.h1, D.h2);
+  int cur = 0;
+  HIPCHK(hipGetDevice(&cur));
+  if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
+  hipError_t e = hipSuccess;
+  if (!h->ev_ctrl) e = hipEventCreateWithFlags(&h->ev_ctrl, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventSynchronize(h->ev_ctrl);   // the previous upload has left the staging buffer
+  if (e == hipSuccess && h->ctrl_stage_floats < nf) {
+    if (h->h_ctrl_stage) hipHostFree(h->h_ctrl_stage);
+    h->h_ctrl_stage = nullptr; h->ctrl_stage_floats = 0;
+    e = hipHostMalloc((void**)&h->h_ctrl_stage, 4 * nf);
+    if (e == hipSuccess) h->ctrl_stage_floats = nf;
+  }
+  if (e == hipSuccess) {
+    mlp_pack(m, h->h_ctrl_stage);
+    e = hipMemcpyAsync(h->ctrl_mem[id], h->h_ctrl_stage, 4 * nf, hipMemcpyHostToDevice, (hipStream_t)stream);
+  }
+  if (e == hipSuccess) e = hipEventRecord(h->ev_ctrl, (hipStream_t)stream);
+  if (cur != h->cfg.device) hipSetDevice(cur);
+  if (e != hipSuccess) return fail("updating controller %d failed: %s", id, hipGetErrorString(e));
+  return 0;
+}
+extern "C" int nascar_set_actor_critic(NascarHandle* h, int32_t pi_id, int32_t vf_id, const float* log_std) {
+  if (!h) return fail("null argument");
+  if (!log_std) { h->ac_set = false; return 0; }
+  const int n = (int)h->ctrl.size();
+  if (pi_id < 0 || pi_id >= n || vf_id < 0 || vf_id >= n)
+    return fail("actor-critic: unknown controller id (pi %d, vf %d; %d loaded with nascar_add_controller)", pi_id, vf_id, n);
+  if (h->ctrl[pi_id].output != MLP_OUT_SAMPLE) return fail("actor-critic: controller %d is no sampled actor (output 4)", pi_id);
+  if (h->ctrl[vf_id].output != MLP_OUT_VALUE) return fail("actor-critic: controller %d is no critic (act_dim 1, output 3)", vf_id);
+  if (!std::isfinite(log_std[0]) || !std::isfinite(log_std[1]))
+    return fail("actor-critic: log_std (%g, %g) is not finite", log_std[0], log_std[1]);
+  h->ac_pi = pi_id; h->ac_vf = vf_id; h->ac_log_std[0] = log_std[0]; h->ac_log_std[1] = log_std[1];
+  h->ac_set = true;
+  return 0;
+}
 extern "C" int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl) {
   if (!h) return fail("null argument");
   if (!ctrl) { h->field_set = false; return 0; }
+  for (int c = 0; c < h->C; ++c)
+    if (ctrl[c] >= 0 && ctrl[c] < (int)h->ctrl.size() && h->ctrl[ctrl[c]].output >= MLP_OUT_VALUE)
+      return fail("car slot %d: controller %d is a critic or a sampled actor (nascar_set_actor_critic), no driver of the field",
+                  c, ctrl[c]);
   for (int c = 0; c < h->C; ++c)
     if (ctrl[c] < NASCAR_CTRL_GENOME || (ctrl[c] == NASCAR_CTRL_GENOME && !h->genome_set) || ctrl[c] >= (int)h->ctrl.size())
       return fail("car slot %d: unknown controller id %d (%d loaded with nascar_add_controller; built-in sources are -1 rule, "
@@ -4989,10 +5130,47 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
   }
   return 0;
 }
+// The actor-critic of nascar_set_actor_critic on the cars [c0, c0 + n) of obs ([N][38], a flat batch: every car slot runs
+// the one pair of nets).  what & AC_SAMPLE: the sampled action of (seed, car, step) -- clip(a) to act, a to actions and its
+// log-probability to logp (either may be null); what & AC_VALUE: V to values; tflags (the step's env_flags): only for
+// the cars of truncated, not terminated envs.  One launch with two grid-y entries when the nets share (h1, h2,
+// activation), else one launch each.
+static int launch_ac(NascarHandle* h, int what, int c0, int n, uint64_t seed, int64_t step, const float* obs, float* act,
+                     float* actions, float* logp, float* values, const uint8_t* tflags, hipStream_t s) {
+  if (n <= 0) return 0;
+  const MlpDev& PI = h->ctrl[h->ac_pi];
+  const MlpDev& VF = h->ctrl[h->ac_vf];
+  MlpLaunch L{};
+  L.table = h->d_ctrl; L.obs = obs; L.act = act; L.env0 = c0; L.nenv = n; L.C = 1;
+  L.values = values; L.actions = actions; L.logp = logp; L.tflags = tflags; L.tcars = h->C;
+  L.log_std[0] = h->ac_log_std[0]; L.log_std[1] = h->ac_log_std[1]; L.seed = seed; L.step = step;
+  const int gx = ((n + 31) / 32 + AM_WAVES - 1) / AM_WAVES;
+  const bool both = (what & AC_SAMPLE) && (what & AC_VALUE);
+  const bool shared = PI.h1 == VF.h1 && PI.h2 == VF.h2 && PI.activation == VF.activation;
+  if (both && shared) {
+    L.slot_id[0] = h->ac_pi << 8; L.slot_id[1] = h->ac_vf << 8;
+    if (!mlp_launch(PI.h1, PI.h2, PI.activation, dim3(gx, 2), s, L)) return fail("no kernel for controller shape %d-%d", PI.h1, PI.h2);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  if (what & AC_SAMPLE) {
+    L.slot_id[0] = h->ac_pi << 8;
+    if (!mlp_launch(PI.h1, PI.h2, PI.activation, dim3(gx, 1), s, L)) return fail("no kernel for controller shape %d-%d", PI.h1, PI.h2);
+    HIPCHK(hipGetLastError());
+  }
+  if (what & AC_VALUE) {
+    L.slot_id[0] = h->ac_vf << 8;
+    if (!mlp_launch(VF.h1, VF.h2, VF.activation, dim3(gx, 1), s, L)) return fail("no kernel for controller shape %d-%d", VF.h1, VF.h2);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}
 extern "C" int nascar_controller_forward(NascarHandle* h, int32_t id, const float* obs, int32_t n, float* actions,
                                          void* stream) {
   if (!h || n < 0) return fail("bad argument");
   if (id < 0 || id >= (int)h->ctrl.size()) return fail("unknown controller id %d (%d loaded)", id, (int)h->ctrl.size());
+  if (h->ctrl[id].output >= MLP_OUT_VALUE)
+    return fail("controller %d is a critic or a sampled actor: it runs as policy 6 (nascar_set_actor_critic)", id);
   if (n == 0) return 0;   // an empty batch has no buffers: its pointers may be null
   if (!obs || !actions) return fail("bad argument");
   if ((uintptr_t)actions & 7) return fail("controller actions must be 8-byte aligned");

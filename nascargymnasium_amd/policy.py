@@ -10,6 +10,10 @@ The reference's race modes (game/competition.py:150-212) put a different control
 A2C checkpoints beside the rule driver.  ``load_sb3_policy`` reads any of the three kinds into a ``Controller``
 record -- a two-hidden-layer MLP 38 -> h1 -> h2 -> 2 with its activation and output transform -- for
 ``BatchedCarEnv.add_controller`` / ``set_car_controllers`` (policy 4, ``mlp_field_kernel``).
+
+The reference's trainers (learn/ppo.py, learn/a2c.py) need the rest of such a checkpoint: ``load_sb3_actor_critic`` reads
+policy net, value net and ``log_std`` into an ``ActorCritic`` record for ``BatchedCarEnv.set_actor_critic`` / ``collect``
+(policy 6: the sampled Gaussian actor and the critic, the same kernel's MLP_OUT_SAMPLE / MLP_OUT_VALUE epilogues).
 """
 import io
 import json
@@ -58,6 +62,8 @@ def actor_arrays(weights: dict):
 # ------------------------------------------------------------------ per-car controllers (policy 4)
 RELU, TANH = 0, 1                       # NascarMlp.activation
 OUT_RAW, OUT_CLIP, OUT_SQUASH = 0, 1, 2  # NascarMlp.output
+OUT_VALUE, OUT_SAMPLE = 3, 4            # a critic's value head / the sampled Gaussian actor (policy 6: ActorCritic)
+MLP_SHAPES = ((256, 256), (256, 128), (256, 32), (128, 128), (64, 64), (32, 256))   # csrc/nascar_actor.h MLP_SHAPES
 SAC_KEYS = ACTOR_KEYS
 AC_KEYS = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias", "mlp_extractor.policy_net.2.weight",
            "mlp_extractor.policy_net.2.bias", "action_net.weight", "action_net.bias")
@@ -133,6 +139,120 @@ def load_sb3_policy(zip_path: str) -> Controller:
         raise ValueError(f"{zip_path}: neither an SB3 SAC actor (actor.latent_pi.* + actor.mu.*) nor an actor-critic "
                          f"policy (mlp_extractor.policy_net.* + action_net.*); keys: {sorted(sd)[:8]}")
     return make_controller([sd[k].float().numpy() for k in keys], act, out, kind)
+
+
+def _sb3_activation(zip_path, data) -> int:
+    kw = data.get("policy_kwargs") or {}
+    fn = str(kw.get("activation_fn", "Tanh")) if isinstance(kw, dict) else "Tanh"
+    if "ReLU" in fn:
+        return RELU
+    if "Tanh" in fn:
+        return TANH
+    raise ValueError(f"{zip_path}: activation_fn {fn!r} is neither ReLU nor Tanh")
+
+
+# ------------------------------------------------------------------ the sampled actor-critic (policy 6, collect)
+VF_KEYS = ("mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias", "mlp_extractor.value_net.2.weight",
+           "mlp_extractor.value_net.2.bias", "value_net.weight", "value_net.bias")
+
+
+class ValueNet(NamedTuple):
+    """A critic 38 -> h1 -> h2 -> 1 in PyTorch layouts: w3 [1, h2], b3 [1]; `activation` on both hidden layers."""
+    w1: np.ndarray
+    b1: np.ndarray
+    w2: np.ndarray
+    b2: np.ndarray
+    w3: np.ndarray
+    b3: np.ndarray
+    h1: int
+    h2: int
+    activation: int
+
+    @property
+    def arrays(self):
+        return (self.w1, self.b1, self.w2, self.b2, self.w3, self.b3)
+
+    output = OUT_VALUE
+
+
+class ActorCritic(NamedTuple):
+    """What SB3's on-policy algorithms (PPO, A2C) train: the Gaussian policy's mean net `pi` (a Controller with OUT_RAW),
+    the critic `vf` and the state-independent `log_std` [2] (float32).  BatchedCarEnv.set_actor_critic / collect."""
+    pi: Controller
+    vf: ValueNet
+    log_std: np.ndarray
+
+
+def make_value_net(arrays, activation: int) -> ValueNet:
+    """A ValueNet from six arrays (PyTorch layouts), checked for a 38 -> h1 -> h2 -> 1 shape the kernels hold: any other
+    (h1, h2) raises, the message naming it."""
+    w1, b1, w2, b2, w3, b3 = [np.ascontiguousarray(np.asarray(a, np.float32)) for a in arrays]
+    if w1.ndim != 2 or w2.ndim != 2 or w3.ndim != 2:
+        raise ValueError("value net weights must be 2-D")
+    h1, h2 = int(w1.shape[0]), int(w2.shape[0])
+    want = ((h1, 38), (h1,), (h2, h1), (h2,), (1, h2), (1,))
+    got = tuple(a.shape for a in (w1, b1, w2, b2, w3, b3))
+    if got != want:
+        raise ValueError(f"value net shapes {got}, expected {want} (obs 38 -> h1 -> h2 -> 1 value)")
+    if activation not in (RELU, TANH):
+        raise ValueError(f"activation {activation} unknown")
+    if (h1, h2) not in MLP_SHAPES:
+        raise ValueError(f"value net shape 38 -> {h1} -> {h2} -> 1 ({'ReLU' if activation == RELU else 'Tanh'}) unsupported: "
+                         f"the kernels hold hidden layers {', '.join('%d-%d' % s for s in MLP_SHAPES)}")
+    return ValueNet(w1, b1, w2, b2, w3, b3, h1, h2, int(activation))
+
+
+def make_actor_critic(pi_arrays, vf_arrays, activation: int, log_std, kind: str = "random") -> ActorCritic:
+    ls = np.ascontiguousarray(np.asarray(log_std, np.float32))
+    if ls.shape != (2,) or not np.all(np.isfinite(ls)):
+        raise ValueError(f"log_std must be 2 finite values, got {ls!r}")
+    return ActorCritic(make_controller(pi_arrays, activation, OUT_RAW, kind), make_value_net(vf_arrays, activation), ls)
+
+
+def load_sb3_actor_critic(zip_path: str) -> ActorCritic:
+    """Policy net, value net and log_std of an SB3 PPO / A2C checkpoint zip (ActorCriticPolicy with an MlpExtractor of
+    two hidden layers per branch: ``mlp_extractor.policy_net.*`` + ``action_net.*``, ``mlp_extractor.value_net.{0,2}.*`` +
+    ``value_net.*``, ``log_std``); the activation as load_sb3_policy reads it.  ``policy.pth`` is read with
+    torch.load(weights_only=True): nothing is unpickled; the optimizer is not read.  A SAC zip, or anything else without
+    these tensors, raises ValueError, as does a value net of a shape the kernels do not hold."""
+    import torch
+    with zipfile.ZipFile(zip_path) as z:
+        sd = torch.load(io.BytesIO(z.read("policy.pth")), weights_only=True, map_location="cpu")
+        data = json.loads(z.read("data")) if "data" in z.namelist() else {}
+    missing = [k for k in AC_KEYS + VF_KEYS + ("log_std",) if k not in sd]
+    if missing:
+        what = "an SB3 SAC checkpoint (no value net, no log_std)" if all(k in sd for k in SAC_KEYS) else "no actor-critic"
+        raise ValueError(f"{zip_path}: {what}: missing {missing[:4]}")
+    act = _sb3_activation(zip_path, data)
+    return make_actor_critic([sd[k].float().numpy() for k in AC_KEYS], [sd[k].float().numpy() for k in VF_KEYS], act,
+                             sd["log_std"].float().numpy(), "actor_critic")
+
+
+def random_actor_critic(h1: int, h2: int, activation: int = TANH, log_std=(0.0, 0.0), seed: int = 0,
+                        vf_shape=None, vf_activation=None) -> ActorCritic:
+    """Random-init actor-critic (PyTorch nn.Linear default init): pi 38 -> h1 -> h2 -> 2, vf 38 -> h1 -> h2 -> 1, or
+    `vf_shape` = (h1, h2) / `vf_activation` for a critic of another shape (it then runs in a launch of its own)."""
+    pi = random_mlp(h1, h2, activation, OUT_RAW, seed)
+    v1, v2 = vf_shape or (h1, h2)
+    rng = np.random.default_rng(seed + 7919)
+    arrs = []
+    for shp, fan_in in (((v1, 38), 38), ((v1,), 38), ((v2, v1), v1), ((v2,), v1), ((1, v2), v2), ((1,), v2)):
+        bound = 1.0 / np.sqrt(fan_in)
+        arrs.append(rng.uniform(-bound, bound, shp).astype(np.float32))
+    ls = np.ascontiguousarray(np.asarray(log_std, np.float32))
+    return ActorCritic(pi, make_value_net(arrs, activation if vf_activation is None else vf_activation), ls)
+
+
+def actor_critic_numpy(ac: ActorCritic, obs, dtype=np.float64):
+    """Host restatement of the actor-critic's forward in `dtype` arithmetic: (mu [n, 2], value [n])."""
+    dt = np.dtype(dtype).type
+    mu = mlp_forward_numpy(ac.pi, obs, dtype, output=OUT_RAW)
+    f = (lambda v: np.maximum(v, dt(0))) if ac.vf.activation == RELU else np.tanh
+    x = np.asarray(obs, dtype=dt).reshape(-1, 38)
+    w1, b1, w2, b2, w3, b3 = [a.astype(dt) for a in ac.vf.arrays]
+    h = f(x @ w1.T + b1)
+    h = f(h @ w2.T + b2)
+    return mu, (h @ w3.T + b3)[:, 0]
 
 
 def random_mlp(h1: int, h2: int, activation: int = RELU, output: int = OUT_RAW, seed: int = 0) -> Controller:
