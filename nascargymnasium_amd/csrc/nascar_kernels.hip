@@ -2859,6 +2859,44 @@ static int fail(const char* fmt, ...) {
 }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s failed: %s", #x, hipGetErrorString(e_)); } while (0)
 
+// Makes `device` current for its scope and hands the caller's current device back at the end, on every way out.
+// err: the switch's status, for the caller to check once.
+struct DeviceGuard {
+  int prev = 0; bool switched = false; hipError_t err;
+  explicit DeviceGuard(int device) {
+    err = hipGetDevice(&prev);
+    if (err == hipSuccess && prev != device) { err = hipSetDevice(device); switched = err == hipSuccess; }
+  }
+  ~DeviceGuard() { if (switched) hipSetDevice(prev); }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+// Pinned host staging of a handle's stream-ordered uploads: the buffer and the event of its last upload.  A user
+// calls reserve(), fills host, enqueues its hipMemcpyAsync calls out of it and calls record().  The handle keeps one
+// per user (track tables, genome table, controller weights), so independent uploads never wait for each other.
+struct PinnedStage {
+  void* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr;
+  // waits until the previous upload has left the buffer, then makes it hold at least `bytes`
+  hipError_t reserve(size_t bytes) {
+    hipError_t e = ev ? hipEventSynchronize(ev) : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess || bytes <= cap) return e;
+    if (host) hipHostFree(host);
+    host = nullptr; cap = 0;
+    e = hipHostMalloc(&host, bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+  }
+  // after the copies out of the buffer are enqueued on `s`
+  hipError_t record(hipStream_t s) { return hipEventRecord(ev, s); }
+  // the event is synchronised before the buffer goes: an upload may still be reading it
+  void release() {
+    if (ev) { hipEventSynchronize(ev); hipEventDestroy(ev); }
+    if (host) hipHostFree(host);
+    host = nullptr; cap = 0; ev = nullptr;
+  }
+};
+
 // persistent actor grid: one workgroup per CU (W2 fills the LDS), never more than the tiles
 static int actor_grid(int n) {
   static int cus = 0;
@@ -2868,345 +2906,7 @@ static int actor_grid(int n) {
 }
 
 
-struct HostGrid {
-  WallGrid g{};
-  std::vector<int> start; std::vector<uint16_t> idx;
-  int* d_start = nullptr; uint16_t* d_idx = nullptr;
-  std::vector<float4> box; float4* d_box = nullptr;
-};
-// host-side wall record: the device's LWall plus the values only the host builders use
-struct HWall : LWall {
-  float rad;                 // bounding radius + culling margin (sensor wall image)
-  float flx, fly, fhx, fhy;  // broadphase fat AABB
-};
-struct HostTrack {
-  std::vector<HWall> walls; std::vector<DSeg> segs; std::vector<double> prefix;
-  double total_length; int startline, has_banking;
-  LWall* d_walls = nullptr; float4* d_wfat = nullptr; DSeg* d_segs = nullptr; double* d_prefix = nullptr;
-  HostGrid bp, sn;
-  struct {
-    BeamGrid g{};
-    std::vector<int4> chunk; std::vector<uint16_t> ent; std::vector<uint2> head;
-    int4* d_chunk = nullptr; uint16_t* d_ent = nullptr; uint2* d_head = nullptr;
-    int nxc = 0;
-    size_t entries = 0, nlist = 0, dropped = 0;   // dropped: cells whose continuations overflow the 16-bit offsets
-    double build_s = 0.0;
-  } beam;
-  std::vector<float4> groups; float4* d_groups = nullptr;
-  float4* d_swall = nullptr;
-};
-
-// Wall grids (see WallGrid in nascar_device.h).  Conservative by construction: the
-// broadphase list of a cell holds every wall whose fat AABB overlaps the cell grown by
-// reach (+5 cm); the sensor list every wall whose culling circle (rad + 0.25 m) comes
-// within 251 m of the cell, nearest first.
-static const float BP_CELL = 4.0f, BP_REACH = 7.0f, SN_CELL = 16.0f, SN_PAD = 20.0f;
-static const double SN_GROUP_R = 12.0; static const int SN_GROUP_N = 8;
-static void build_grids(HostTrack& t) {
-  double lx = 1e30, ly = 1e30, hx = -1e30, hy = -1e30;
-  for (auto& w : t.walls) { lx = std::min(lx, (double)w.flx); ly = std::min(ly, (double)w.fly);
-                            hx = std::max(hx, (double)w.fhx); hy = std::max(hy, (double)w.fhy); }
-  auto setup = [&](HostGrid& G, float cell, float pad, float reach) {
-    G.g.ox = (float)(lx - pad); G.g.oy = (float)(ly - pad); G.g.inv_cell = 1.0f / cell; G.g.reach = reach;
-    G.g.nx = (int)std::ceil((hx + pad - G.g.ox) / cell) + 1; G.g.ny = (int)std::ceil((hy + pad - G.g.oy) / cell) + 1;
-    G.start.assign((size_t)G.g.nx * G.g.ny + 1, 0);
-  };
-  setup(t.bp, BP_CELL, BP_REACH + 4.0f, BP_REACH);
-  setup(t.sn, SN_CELL, SN_PAD, 0.0f);
-  const int nw = (int)t.walls.size();
-  for (int cy = 0; cy < t.bp.g.ny; ++cy)
-    for (int cx = 0; cx < t.bp.g.nx; ++cx) {
-      const double x0 = t.bp.g.ox + (double)cx * BP_CELL - BP_REACH - 0.05, x1 = t.bp.g.ox + (double)(cx + 1) * BP_CELL + BP_REACH + 0.05;
-      const double y0 = t.bp.g.oy + (double)cy * BP_CELL - BP_REACH - 0.05, y1 = t.bp.g.oy + (double)(cy + 1) * BP_CELL + BP_REACH + 0.05;
-      t.bp.start[(size_t)cy * t.bp.g.nx + cx] = (int)t.bp.idx.size();
-      for (int j = 0; j < nw; ++j) {
-        const HWall& w = t.walls[j];
-        if (w.flx > x1 || w.fhx < x0 || w.fly > y1 || w.fhy < y0) continue;
-        t.bp.idx.push_back((uint16_t)j);
-        t.bp.box.push_back(make_float4(w.flx, w.fly, w.fhx, w.fhy));
-      }
-    }
-  t.bp.start.back() = (int)t.bp.idx.size();
-  for (int k = 0; k < std::max(BP_BATCH, 1); ++k) t.bp.box.push_back(make_float4(1e30f, 1e30f, -1e30f, -1e30f));
-  // sensor wall groups: runs of consecutive walls (index order follows each boundary through
-  // the curves) whose corners fit in a circle of radius <= SN_GROUP_R, at most SN_GROUP_N walls
-  {
-    auto corners = [&](int j, double* xs, double* ys) {
-      const LWall& w = t.walls[j];
-      const float vx[4] = {-w.hx, w.hx, w.hx, -w.hx}, vy[4] = {-w.hy, -w.hy, w.hy, w.hy};
-      for (int i = 0; i < 4; ++i) { xs[i] = (w.qc * vx[i] - w.qs * vy[i]) + w.px; ys[i] = (w.qs * vx[i] + w.qc * vy[i]) + w.py; }
-    };
-    auto circle = [&](int first, int count, double& cx, double& cy) {
-      double lx = 1e30, ly = 1e30, ux = -1e30, uy = -1e30, xs[4], ys[4];
-      for (int j = first; j < first + count; ++j) {
-        corners(j, xs, ys);
-        for (int i = 0; i < 4; ++i) { lx = std::min(lx, xs[i]); ux = std::max(ux, xs[i]); ly = std::min(ly, ys[i]); uy = std::max(uy, ys[i]); }
-      }
-      cx = 0.5 * (lx + ux); cy = 0.5 * (ly + uy);
-      double r = 0.0;
-      for (int j = first; j < first + count; ++j) {
-        corners(j, xs, ys);
-        for (int i = 0; i < 4; ++i) r = std::max(r, std::hypot(xs[i] - cx, ys[i] - cy));
-      }
-      return r;
-    };
-    t.groups.clear();
-    int first = 0;
-    while (first < nw) {
-      int count = 1;
-      while (first + count < nw && count < SN_GROUP_N) {
-        double cx, cy;
-        if (circle(first, count + 1, cx, cy) > SN_GROUP_R) break;
-        ++count;
-      }
-      double cx, cy, r = circle(first, count, cx, cy);
-      const int packed = first | (count << 16);
-      float pf; memcpy(&pf, &packed, sizeof pf);
-      t.groups.push_back(make_float4((float)cx, (float)cy, (float)(r + 0.3), pf));
-      first += count;
-    }
-  }
-  std::vector<std::pair<double, int>> cand;
-  const int ng = (int)t.groups.size();
-  for (int cy = 0; cy < t.sn.g.ny; ++cy)
-    for (int cx = 0; cx < t.sn.g.nx; ++cx) {
-      const double x0 = t.sn.g.ox + (double)cx * SN_CELL, x1 = x0 + SN_CELL;
-      const double y0 = t.sn.g.oy + (double)cy * SN_CELL, y1 = y0 + SN_CELL;
-      const double mx = 0.5 * (x0 + x1), my = 0.5 * (y0 + y1);
-      t.sn.start[(size_t)cy * t.sn.g.nx + cx] = (int)t.sn.idx.size();
-      cand.clear();
-      for (int g = 0; g < ng; ++g) {
-        const float4 G = t.groups[g];
-        const double dx = std::max(std::max(x0 - G.x, 0.0), G.x - x1), dy = std::max(std::max(y0 - G.y, 0.0), G.y - y1);
-        if (std::sqrt(dx * dx + dy * dy) > 251.0 + G.z) continue;
-        cand.push_back({std::hypot(G.x - mx, G.y - my) - G.z, g});
-      }
-      std::sort(cand.begin(), cand.end());
-      for (auto& c : cand) t.sn.idx.push_back((uint16_t)c.second);
-    }
-  t.sn.start.back() = (int)t.sn.idx.size();
-}
-// Beam lists (BeamGrid).  Cells of `cell` m (BEAM_CELL_M by default) over the walls' extent; a cell gets lists when its centre is
-// within (largest half width + BEAM_BAND) of a wall centre line -- the corridor and a band outside each wall.
-// Per cell (centre c, disk radius rc = half diagonal + 5 cm) and wall j (centre line AB, capsule radius
-// rr = half thickness + 10 cm, which holds the box and the f32 rounding of the device's ray cast):
-//  * lb = dist(c, AB) - rr - rc bounds the distance from any ray origin in the cell to any point of the box;
-//    walls with lb > 251 m are out of the 250 m ray's reach;
-//  * the directions from the disk to the capsule lie in the arc between the directions from c to A and to
-//    B, widened by asin((rr + rc) / dist(c, AB)) (all bins when c is inside the grown capsule), plus a
-//    2e-3 rad guard for the f32 ray end points; every bin that arc touches lists the wall.
-// Both are conservative, so the walk in ray_sensor_kernel visits every wall that can be the first hit.
-// Cell size: the cell's disk widens every wall's angular arc and lowers its distance bound, so smaller cells give
-// shorter walks (steady-state sensor tails; bench step 191 -> 178 / 174 / 168 / 167 us at 2 / 1.5 / 1 / 0.75 m,
-// round 4) at 0.2-0.5 GB of lists per track at 1 m (8-byte heads + sentinel-terminated continuations).
-#define BEAM_CELL_M 1.0f
-#define BEAM_CELL_MIN 0.5f    // nascar_set_beam_cell range (heads: cell count x 4 KB; walks: longer above ~2 m)
-#define BEAM_CELL_MAX 8.0f
-static const double BEAM_BAND = 8.0;
-static void build_beams(HostTrack& t, const float cell) {
-  auto t0 = std::chrono::steady_clock::now();
-  auto& B = t.beam;
-  const int nw = (int)t.walls.size();
-  std::vector<double> ax(nw), ay(nw), bx(nw), by(nw), rr(nw);
-  double lx = 1e30, ly = 1e30, ux = -1e30, uy = -1e30, hwmax = 0.0;
-  for (int j = 0; j < nw; ++j) {
-    const LWall& w = t.walls[j];
-    const double ex = (double)w.hx * w.qc, ey = (double)w.hx * w.qs;
-    ax[j] = w.px - ex; ay[j] = w.py - ey; bx[j] = w.px + ex; by[j] = w.py + ey;
-    rr[j] = (double)w.hy + 0.1;
-    lx = std::min({lx, ax[j], bx[j]}); ux = std::max({ux, ax[j], bx[j]});
-    ly = std::min({ly, ay[j], by[j]}); uy = std::max({uy, ay[j], by[j]});
-  }
-  for (auto& s : t.segs) hwmax = std::max(hwmax, s.width / 2.0);
-  const double D = hwmax + BEAM_BAND, pad = D + 2.0 * cell;
-  B.g.ox = (float)(lx - pad); B.g.oy = (float)(ly - pad); B.g.inv_cell = 1.0f / cell;
-  B.g.nx = (int)std::ceil((ux + pad - B.g.ox) / cell) + 1;
-  B.g.ny = (int)std::ceil((uy + pad - B.g.oy) / cell) + 1;
-  const int nx = B.g.nx, ny = B.g.ny;
-  auto segdist = [&](int j, double x, double y) {
-    const double sx = bx[j] - ax[j], sy = by[j] - ay[j], ll = sx * sx + sy * sy;
-    double tt = ll > 0 ? ((x - ax[j]) * sx + (y - ay[j]) * sy) / ll : 0.0;
-    tt = std::min(1.0, std::max(0.0, tt));
-    return std::hypot(x - (ax[j] + tt * sx), y - (ay[j] + tt * sy));
-  };
-  auto centre = [&](int cx, int cy, double& x, double& y) {
-    x = (double)B.g.ox + (cx + 0.5) * (double)cell; y = (double)B.g.oy + (cy + 0.5) * (double)cell;
-  };
-  // cells near a wall
-  std::vector<uint8_t> mark((size_t)nx * ny, 0);
-  for (int j = 0; j < nw; ++j) {
-    const int x0 = std::max(0, (int)std::floor((std::min(ax[j], bx[j]) - D - B.g.ox) / cell) - 1);
-    const int x1 = std::min(nx - 1, (int)std::floor((std::max(ax[j], bx[j]) + D - B.g.ox) / cell) + 1);
-    const int y0 = std::max(0, (int)std::floor((std::min(ay[j], by[j]) - D - B.g.oy) / cell) - 1);
-    const int y1 = std::min(ny - 1, (int)std::floor((std::max(ay[j], by[j]) + D - B.g.oy) / cell) + 1);
-    for (int cy = y0; cy <= y1; ++cy)
-      for (int cx = x0; cx <= x1; ++cx) {
-        double x, y;
-        centre(cx, cy, x, y);
-        if (segdist(j, x, y) <= D) mark[(size_t)cy * nx + cx] = 1;
-      }
-  }
-  // entry layout: 10 wall bits up to 1024 walls (6-bit codes of c^2 / 16 m), then one more per doubling; the code scale
-  // keeps the largest non-sentinel code near 240 m (a 250 m ray)
-  uint32_t wb = 10;
-  while (wb < BEAM_MAX_WALL_BITS && nw > (1 << wb)) ++wb;
-  B.g.wbits = wb; B.g.wmask = (1u << wb) - 1u; B.g.cmax = (1u << (16 - wb)) - 1u;
-  B.g.kq = (float)(0.0625 * std::pow(62.0 / (double)(B.g.cmax - 1), 2.0));
-  std::vector<int> cells;   // the marked cells, row-major
-  if (nw <= (1 << BEAM_MAX_WALL_BITS))   // (more walls than the entries address: no lists, the wall-group walk)
-    for (size_t k = 0; k < mark.size(); ++k)
-      if (mark[k]) cells.push_back((int)k);
-  const int ncell = (int)cells.size();
-  const double rc = cell * 0.70710678 + 0.05, two_pi = 2.0 * M_PI, dbin = two_pi / BEAM_NB;
-  std::vector<std::vector<uint32_t>> lists((size_t)ncell * BEAM_NB);
-  auto work = [&](int c0, int c1) {
-    for (int ci = c0; ci < c1; ++ci) {
-      double x, y;
-      centre(cells[ci] % nx, cells[ci] / nx, x, y);
-      std::vector<uint32_t>* L = &lists[(size_t)ci * BEAM_NB];
-      for (int j = 0; j < nw; ++j) {
-        const double d = segdist(j, x, y), R = rr[j] + rc, lb = d - R;
-        if (lb > 251.0) continue;
-        const uint32_t q = (uint32_t)std::min(65535.0, std::floor(std::max(lb, 0.0) * 100.0));
-        const uint32_t e = (q << 16) | (uint32_t)j;
-        if (d <= R * 1.0001 + 1e-3) { for (int k = 0; k < BEAM_NB; ++k) L[k].push_back(e); continue; }
-        const double aA = std::atan2(ay[j] - y, ax[j] - x), aB = std::atan2(by[j] - y, bx[j] - x);
-        double dl = aB - aA;
-        while (dl > M_PI) dl -= two_pi;
-        while (dl <= -M_PI) dl += two_pi;
-        const double a0 = dl >= 0 ? aA : aB, span = std::fabs(dl);
-        const double wid = std::asin(std::min(1.0, R / d)) + 2e-3;
-        const long k0 = (long)std::floor((a0 - wid) / dbin), k1 = (long)std::floor((a0 + span + wid) / dbin);
-        if (k1 - k0 + 1 >= BEAM_NB) { for (int k = 0; k < BEAM_NB; ++k) L[k].push_back(e); continue; }
-        for (long k = k0; k <= k1; ++k) L[((k % BEAM_NB) + BEAM_NB) % BEAM_NB].push_back(e);
-      }
-      for (int k = 0; k < BEAM_NB; ++k) std::sort(L[k].begin(), L[k].end());
-    }
-  };
-  const int nth = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
-  std::vector<std::thread> th;
-  for (int k = 0; k < nth; ++k) th.emplace_back(work, (int)((long)ncell * k / nth), (int)((long)ncell * (k + 1) / nth));
-  for (auto& x : th) x.join();
-  // 16-bit entries: the bound code c = floor(sqrt(bound / kq)), so c^2 kq <= the wall's bound (rounded down again where
-  // the double sqrt rounded up onto an integer), at most cmax - 1; each list sorted by entry, so the codes ascend
-  const uint32_t cmax = B.g.cmax;
-  const double kq = (double)B.g.kq;
-  auto code_of = [&](uint32_t e) {
-    const double lb = (double)(e >> 16) * 0.01;   // the cm bound, itself rounded down
-    int c = (int)std::min<double>((double)cmax - 1.0, std::floor(std::sqrt(lb / kq)));
-    while (c > 0 && (double)(c * c) * kq > lb) --c;
-    return (uint16_t)(((uint32_t)c << wb) | (e & 0xFFFFu));
-  };
-  // per list (cell-major, slot order, beam_slot): the head record holds its first BEAM_HEAD entries (BEAM_PAD filled)
-  // and, when the list is longer, 1 + the offset of its continuation -- the remaining entries followed by one BEAM_PAD
-  // sentinel, so a walk needs no list end -- from its chunk's first ent[] index.  ent[0] is a sentinel; BEAM_COOP_PAD
-  // sentinels close the array (the chunked and the wave-cooperative walks read past a list's sentinel).  A cell whose
-  // continuations would overflow its chunk's 16-bit offsets keeps no lists (its rays take the wall-group walk).
-  B.nxc = (nx + BEAM_CHUNK - 1) / BEAM_CHUNK;
-  B.chunk.assign((size_t)B.nxc * ny, make_int4(-1, 0, 0, 0));
-  std::vector<uint8_t> keep(ncell, 1);
-  B.dropped = 0;
-  for (int c0 = 0, c1; c0 < ncell; c0 = c1) {   // cells of one chunk: consecutive in row-major order
-    const int key = cells[c0] / nx * B.nxc + cells[c0] % nx / BEAM_CHUNK;
-    for (c1 = c0; c1 < ncell && cells[c1] / nx * B.nxc + cells[c1] % nx / BEAM_CHUNK == key; ++c1) {}
-    size_t used = 0;
-    for (int ci = c0; ci < c1; ++ci) {
-      size_t cont = 0;
-      for (int slot = 0; slot < BEAM_NB; ++slot) {
-        const size_t len = lists[(size_t)ci * BEAM_NB + slot].size();
-        if (len > (size_t)BEAM_HEAD) cont += len - BEAM_HEAD + 1;
-      }
-      if (used + cont >= BEAM_CONT_MAX) { keep[ci] = 0; ++B.dropped; } else used += cont;
-    }
-  }
-  const size_t nkept = (size_t)ncell - B.dropped, nlist = nkept * BEAM_NB;
-  B.head.assign(nlist, make_uint2(BEAM_PAD | (BEAM_PAD << 16), BEAM_PAD));
-  B.ent.assign(1, (uint16_t)BEAM_PAD);
-  B.entries = 0;
-  std::vector<uint16_t> L16;
-  int id = 0, cur = -1;
-  size_t cb = 0;
-  for (int ci = 0; ci < ncell; ++ci) {
-    if (!keep[ci]) continue;
-    const int cx = cells[ci] % nx, cy = cells[ci] / nx, key = cy * B.nxc + cx / BEAM_CHUNK;
-    int4& ch = B.chunk[key];
-    if (key != cur) { cur = key; cb = B.ent.size(); ch = make_int4(id * BEAM_NB, (int)cb, 0, 0); }
-    ch.z = (int)((uint32_t)ch.z | (1u << (cx % BEAM_CHUNK)));
-    for (int slot = 0; slot < BEAM_NB; ++slot) {
-      const auto& L = lists[(size_t)ci * BEAM_NB + beam_bin(slot)];
-      B.entries += L.size();
-      L16.resize(L.size());
-      for (size_t k = 0; k < L.size(); ++k) L16[k] = code_of(L[k]);
-      std::sort(L16.begin(), L16.end());
-      uint32_t h[4];
-      for (int k = 0; k < BEAM_HEAD; ++k) h[k] = (size_t)k < L16.size() ? L16[k] : BEAM_PAD;
-      h[3] = 0u;
-      if (L16.size() > (size_t)BEAM_HEAD) {
-        h[3] = (uint32_t)(B.ent.size() - cb) + 1u;
-        B.ent.insert(B.ent.end(), L16.begin() + BEAM_HEAD, L16.end());
-        B.ent.push_back((uint16_t)BEAM_PAD);
-      }
-      B.head[(size_t)id * BEAM_NB + slot] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
-    }
-    ++id;
-  }
-  for (int k = 0; k < (RAY_CHUNK > BEAM_COOP_PAD ? RAY_CHUNK : BEAM_COOP_PAD); ++k) B.ent.push_back((uint16_t)BEAM_PAD);
-  if (getenv("NASCAR_VERBOSE"))
-    fprintf(stderr, "build_beams: %d walls (%u-bit wall indices, bound codes of %.4f m x c^2), %d cells with lists, %zu "
-            "dropped (continuation offsets), %zu entries, heads %.1f MB + continuations %.1f MB\n", nw, B.g.wbits,
-            (double)B.g.kq, ncell - (int)B.dropped, B.dropped, B.entries, 8.0 * B.head.size() / 1e6, 2.0 * B.ent.size() / 1e6);
-  B.nlist = nlist;
-  B.build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
-static int upload_beams(HostTrack& t) {
-  auto& B = t.beam;
-  if (B.ent.size() >= 0x7FFFFFF0u) return fail("beam list continuations hold %zu entries (31-bit cell offsets)", B.ent.size());
-  HIPCHK(hipMalloc(&B.d_chunk, sizeof(int4) * std::max<size_t>(B.chunk.size(), 1)));
-  if (!B.chunk.empty()) HIPCHK(hipMemcpy(B.d_chunk, B.chunk.data(), sizeof(int4) * B.chunk.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&B.d_ent, sizeof(uint16_t) * std::max<size_t>(B.ent.size(), 1)));
-  if (!B.ent.empty()) HIPCHK(hipMemcpy(B.d_ent, B.ent.data(), sizeof(uint16_t) * B.ent.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&B.d_head, sizeof(uint2) * std::max<size_t>(B.head.size(), 1)));
-  if (!B.head.empty()) HIPCHK(hipMemcpy(B.d_head, B.head.data(), sizeof(uint2) * B.head.size(), hipMemcpyHostToDevice));
-  B.g.chunk = B.d_chunk; B.g.nxc = B.nxc; B.g.ent = B.d_ent; B.g.head = B.d_head;
-  return 0;
-}
-
-static int upload_grid(HostGrid& G) {
-  HIPCHK(hipMalloc(&G.d_start, sizeof(int) * G.start.size()));
-  HIPCHK(hipMemcpy(G.d_start, G.start.data(), sizeof(int) * G.start.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&G.d_idx, sizeof(uint16_t) * std::max<size_t>(G.idx.size(), 1)));
-  if (!G.idx.empty()) HIPCHK(hipMemcpy(G.d_idx, G.idx.data(), sizeof(uint16_t) * G.idx.size(), hipMemcpyHostToDevice));
-  G.g.start = G.d_start; G.g.idx = G.d_idx; G.g.box = nullptr;
-  if (!G.box.empty()) {
-    HIPCHK(hipMalloc(&G.d_box, sizeof(float4) * G.box.size()));
-    HIPCHK(hipMemcpy(G.d_box, G.box.data(), sizeof(float4) * G.box.size(), hipMemcpyHostToDevice));
-    G.g.box = G.d_box;
-  }
-  return 0;
-}
-
-// A built track: the device tables of one .track (walls, segments, grids, beam lists, sensor image), read-only
-// once built.  Handles share them through a process-wide cache keyed by the track's input arrays and the device:
-// every env of a batch, every VecEnv sub-engine and every later handle on the same track uses one copy (the beam
-// lists are 0.2-0.5 GB per track at 1 m cells and take ~2 s of host time to build).  The last handle to drop a
-// build frees its device memory.
-struct TrackBuild {
-  int device = 0;
-  HostTrack t;
-  size_t lds = 0;   // model_kernel's LDS wall table
-  ~TrackBuild() {
-    int cur = 0;
-    hipGetDevice(&cur);
-    if (cur != device) hipSetDevice(device);
-    hipFree(t.d_walls); hipFree(t.d_wfat); hipFree(t.d_segs); hipFree(t.d_prefix);
-    hipFree(t.bp.d_start); hipFree(t.bp.d_idx); hipFree(t.bp.d_box); hipFree(t.sn.d_start); hipFree(t.sn.d_idx);
-    hipFree(t.d_groups); hipFree(t.d_swall);
-    hipFree(t.beam.d_chunk); hipFree(t.beam.d_ent); hipFree(t.beam.d_head);
-    if (cur != device) hipSetDevice(cur);
-  }
-};
-static std::mutex g_track_mu;
-static std::unordered_map<std::string, std::weak_ptr<TrackBuild>> g_track_cache;
+#include "nascar_host_track.h"
 
 struct NascarHandle {
   NascarConfig cfg;
@@ -3253,14 +2953,14 @@ struct NascarHandle {
   int field[MLP_MAX_CARS];
   // the sampled actor-critic (policy 6, nascar_collect): controller ids of the Gaussian actor (output MLP_OUT_SAMPLE) and
   // the critic (MLP_OUT_VALUE), log_std, the terminal-observation scratch [N][38] of the timeout values, and the pinned
-  // staging of nascar_update_controller's stream-ordered uploads (ev_ctrl: the staging buffer is free again)
+  // staging of nascar_update_controller's stream-ordered uploads
   bool ac_set = false; int ac_pi = -1, ac_vf = -1; float ac_log_std[2] = {0.0f, 0.0f};
   float* d_term = nullptr;
-  float* h_ctrl_stage = nullptr; size_t ctrl_stage_floats = 0; hipEvent_t ev_ctrl = nullptr;
+  PinnedStage ctrl_stage;
   // genome drivers (policy 5, NASCAR_CTRL_GENOME): the per-car gene records, outside the state arena; their upload is
-  // staged in pinned memory and ordered on the caller's stream (ev_genome: the staging buffer is free again)
+  // staged in pinned memory and ordered on the caller's stream
   GenomeRec* d_genome = nullptr; bool genome_set = false;
-  GenomeRec* h_genome = nullptr; hipEvent_t ev_genome = nullptr;
+  PinnedStage genome_stage;
   // on-device fitness (nascar_set_fitness): one allocation -- acc [FIT_N][N] float64, ended [E], env flags [E] of the
   // steps whose caller passed none
   double* d_fit = nullptr; uint8_t* d_fit_ended = nullptr; uint8_t* d_fit_flags = nullptr; bool fit_on = false;
@@ -3282,8 +2982,7 @@ struct NascarHandle {
   hipEvent_t step_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // nascar_set_step_events (profiling)
   // prepare(): capacities of the track table / block map buffers, pinned staging of their stream-ordered uploads
   size_t cap_tracks = 0, cap_blocks = 0, cap_blk_env = 0;
-  void* h_stage = nullptr; size_t stage_bytes = 0;
-  hipEvent_t ev_stage = nullptr;
+  PinnedStage table_stage;
   // random-track mode (nascar_set_random_tracks): the env -> track map, draw counters and seeds live on the device and
   // the block map is rebuilt there (block_map_kernel) after every launch that may change a track -- no host round trip
   int rt_on = 0, rt_ntracks = 0;
@@ -3418,6 +3117,9 @@ extern "C" int nascar_create(const NascarConfig* cfg, NascarHandle** out) {
 
 extern "C" void nascar_destroy(NascarHandle* h) {
   if (!h) return;
+  // the staged uploads first: each waits for its last copy, so neither the pinned source nor the device destination
+  // of an upload still in flight is freed below
+  h->table_stage.release(); h->genome_stage.release(); h->ctrl_stage.release();
   hipFree(h->d_vhist);
   hipFree(h->arena); hipFree(h->d_pose); hipFree(h->d_pose_cs); hipFree(h->d_ray_cs); hipFree(h->d_actor); hipFree(h->d_actor32); hipFree(h->d_params);
   hipFree(h->d_pipe_ring); hipFree(h->d_pipe_ctr); hipFree(h->d_pipe_sdone);
@@ -3426,8 +3128,6 @@ extern "C" void nascar_destroy(NascarHandle* h) {
     h->tracks.clear();
   }
   hipFree(h->d_tracks); hipFree(h->d_blk_track); hipFree(h->d_blk_env);
-  if (h->ev_stage) { hipEventSynchronize(h->ev_stage); hipEventDestroy(h->ev_stage); }
-  if (h->h_stage) hipHostFree(h->h_stage);
   for (auto st : h->sub_stream) hipStreamDestroy(st);
   for (auto ev : h->ev_join) hipEventDestroy(ev);
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -3435,23 +3135,12 @@ extern "C" void nascar_destroy(NascarHandle* h) {
   for (void* p : h->ctrl_mem) hipFree(p);
   hipFree(h->d_ctrl);
   hipFree(h->d_term);
-  if (h->ev_ctrl) { hipEventSynchronize(h->ev_ctrl); hipEventDestroy(h->ev_ctrl); }
-  if (h->h_ctrl_stage) hipHostFree(h->h_ctrl_stage);
   hipFree(h->d_rt);
-  if (h->ev_genome) { hipEventSynchronize(h->ev_genome); hipEventDestroy(h->ev_genome); }
-  if (h->h_genome) hipHostFree(h->h_genome);
   hipFree(h->d_genome);
   hipFree(h->d_fit);
   delete h;
 }
 
-static int sensor_lds_reserve(size_t need);
-static int host_track(HostTrack& t, const std::string& key, const double* segments, int32_t nseg, double total_length,
-                      const double* walls, int32_t nwall, float beam_cell, int* loaded = nullptr);
-static std::string track_key(const double* segments, int32_t nseg, double total_length, const double* walls,
-                             int32_t nwall, float beam_cell);
-static int upload_track(HostTrack& t, size_t& lds_out);
-static void retain_build(const std::shared_ptr<TrackBuild>& tb);
 // wall table exactly as Box2D sees it (float32 transform via glibc sinf/cosf, fat AABB, key)
 extern "C" int nascar_add_track(NascarHandle* h, const double* segments, int32_t nseg, double total_length,
                                 const double* walls, int32_t nwall) {
@@ -3469,25 +3158,19 @@ extern "C" int nascar_add_track(NascarHandle* h, const double* segments, int32_t
   if (!tb) {
     tb = std::make_shared<TrackBuild>();
     tb->device = h->cfg.device;
-    int cur = 0;
-    HIPCHK(hipGetDevice(&cur));
-    if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
-    int rc = host_track(tb->t, dkey, segments, nseg, total_length, walls, nwall, h->beam_cell);
-    if (rc == 0) rc = upload_track(tb->t, tb->lds);
-    if (cur != h->cfg.device) hipSetDevice(cur);
-    if (rc < 0) return rc;
+    DeviceGuard on(h->cfg.device);
+    HIPCHK(on.err);
+    if (host_track(tb->t, dkey, segments, nseg, total_length, walls, nwall, h->beam_cell) || upload_track(tb->t, tb->lds))
+      return -1;
     g_track_cache[key] = tb;
   }
   retain_build(tb);
   const HostTrack& t = tb->t;
   const size_t need = 2 * sizeof(float4) * t.walls.size() + sizeof(float4) * t.groups.size();
   if (need > h->max_sensor_lds) {   // on the handle's device (the attribute is per device), cached track or not
-    int cur = 0;
-    HIPCHK(hipGetDevice(&cur));
-    if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
-    const int rc = sensor_lds_reserve(need);
-    if (cur != h->cfg.device) hipSetDevice(cur);
-    if (rc < 0) return rc;
+    DeviceGuard on(h->cfg.device);
+    HIPCHK(on.err);
+    if (sensor_lds_reserve(need)) return -1;
   }
   h->max_sensor_lds = std::max(h->max_sensor_lds, need);
   h->max_sensor_groups_lds = std::max(h->max_sensor_groups_lds, sizeof(float4) * t.groups.size());
@@ -3497,234 +3180,6 @@ extern "C" int nascar_add_track(NascarHandle* h, const double* segments, int32_t
   return (int)h->tracks.size() - 1;
 }
 
-// The sensor wall image (2 float4 per wall + 1 per wall group) lives in the dynamic LDS of the kernels that stage it
-// (ray_sensor_kernel, the fused rollout_kernel); with their static LDS it must fit the CU's 160 KiB, so that bounds
-// the walls a track may have (~4 000 with the fused rollout's static LDS, ~4 900 for the sensor kernel alone; the
-// bundled tracks have 730-732).  Images beyond 64 KiB are declared to the runtime first.
-static int sensor_lds_reserve(size_t need) {
-  const void* kern[] = {(const void*)ray_sensor_kernel<4>, (const void*)ray_sensor_kernel<16>,
-                        (const void*)ray_sensor_kernel<16, 512>, (const void*)ray_sensor_kernel<16, 1024>,
-                        (const void*)ray_sensor_kernel<4, BLOCK, false, true>, (const void*)ray_sensor_kernel<16, BLOCK, false, true>,
-                        (const void*)ray_sensor_kernel<16, 512, false, true>, (const void*)ray_sensor_kernel<16, 1024, false, true>,
-                        (const void*)rollout_kernel};
-  for (const void* k : kern) {
-    hipFuncAttributes a;
-    if (hipFuncGetAttributes(&a, k) != hipSuccess) return fail("hipFuncGetAttributes failed");
-    // the fused rollout kernel also holds the car-car extension's scratch after the wall image
-    const size_t n2 = k == (const void*)rollout_kernel ? ((need + 15) & ~(size_t)15) + CC_LDS_BYTES : need;
-    if (a.sharedSizeBytes + n2 > LDS_PER_CU)
-      return fail("track needs %zu B of LDS for its sensor wall image; with %zu B of static LDS a workgroup has %zu",
-                  need, (size_t)a.sharedSizeBytes, LDS_PER_CU - (size_t)a.sharedSizeBytes);
-    if (n2 > 64 * 1024) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n2));
-  }
-  return 0;
-}
-// the host tables of one track (nascar_add_track): walls as Box2D sees them, segments, grids, beam lists, wall groups
-static int host_build_track(HostTrack& t, const double* segments, int32_t nseg, double total_length,
-                            const double* walls, int32_t nwall, float beam_cell) {
-  t.total_length = total_length;
-  t.startline = -1; t.has_banking = 0;
-  double pre = 0.0;
-  for (int k = 0; k < nseg; ++k) {
-    const double* s = segments + 13 * k;
-    DSeg d;
-    d.sx = s[2]; d.sy = s[3]; d.ex = s[4]; d.ey = s[5]; d.width = s[6]; d.banking = s[12];
-    double br = d.banking * (M_PI / 180.0);
-    d.la = (1500.0 * 9.81) * sin(fabs(br)) * 0.3;     // src/car.py:527-533
-    d.chord = sqrt(pow(d.ex - d.sx, 2.0) + pow(d.ey - d.sy, 2.0));
-    t.prefix.push_back(pre);
-    pre += d.chord;
-    t.segs.push_back(d);
-    if (t.startline < 0 && (int)s[0] == 1) t.startline = k;
-    if (fabs(d.banking) >= 0.1) t.has_banking = 1;
-  }
-  std::unordered_map<std::string, int> keys;
-  for (int j = 0; j < nwall; ++j) {
-    const double* w = walls + 4 * j;
-    HWall L;
-    memset(&L, 0, sizeof L);
-    L.px = (float)w[0]; L.py = (float)w[1]; L.ang = (float)w[2];
-    L.qs = sinf(L.ang); L.qc = cosf(L.ang);
-    L.hx = (float)w[3]; L.hy = (float)(1.0 / 2);
-    L.rad = sqrtf(L.hx * L.hx + L.hy * L.hy) + 0.02f;
-    float lx = 0, ly = 0, ux = 0, uy = 0;
-    const float vx[4] = {-L.hx, L.hx, L.hx, -L.hx}, vy[4] = {-L.hy, -L.hy, L.hy, L.hy};
-    for (int i = 0; i < 4; ++i) {
-      float x = (L.qc * vx[i] - L.qs * vy[i]) + L.px;
-      float y = (L.qs * vx[i] + L.qc * vy[i]) + L.py;
-      if (i == 0) { lx = ux = x; ly = uy = y; }
-      else { lx = x < lx ? x : lx; ly = y < ly ? y : ly; ux = ux > x ? ux : x; uy = uy > y ? uy : y; }
-    }
-    const float r = 2.0f * 0.005f;
-    L.flx = (lx - r) - 0.1f; L.fly = (ly - r) - 0.1f; L.fhx = (ux + r) + 0.1f; L.fhy = (uy + r) + 0.1f;
-    char kbuf[96];
-    snprintf(kbuf, sizeof kbuf, "wall_%.1f_%.1f", (double)L.px, (double)L.py);
-    auto it = keys.find(kbuf);
-    if (it == keys.end()) { int id = (int)keys.size(); keys.emplace(kbuf, id); L.key = id; }
-    else L.key = it->second;
-    t.walls.push_back(L);
-  }
-  if (nwall > 65535) return fail("track has %d walls (grid and beam-list indices are 16-bit)", nwall);
-  build_grids(t);
-  build_beams(t, beam_cell);
-  return 0;
-}
-// the device tables of a host-built (or cache-loaded) track, on the current device; lds: model_kernel's wall table bytes.
-// The beam lists' host copies are released afterwards (the device copies are all the kernels use).
-static int upload_track(HostTrack& t, size_t& lds_out) {
-  {
-    std::vector<LWall> dw(t.walls.begin(), t.walls.end());
-    std::vector<float4> fat(t.walls.size());
-    for (size_t j = 0; j < t.walls.size(); ++j) fat[j] = make_float4(t.walls[j].flx, t.walls[j].fly, t.walls[j].fhx, t.walls[j].fhy);
-    HIPCHK(hipMalloc(&t.d_walls, sizeof(LWall) * dw.size()));
-    HIPCHK(hipMemcpy(t.d_walls, dw.data(), sizeof(LWall) * dw.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&t.d_wfat, sizeof(float4) * fat.size()));
-    HIPCHK(hipMemcpy(t.d_wfat, fat.data(), sizeof(float4) * fat.size(), hipMemcpyHostToDevice));
-  }
-  HIPCHK(hipMalloc(&t.d_segs, sizeof(DSeg) * t.segs.size()));
-  HIPCHK(hipMemcpy(t.d_segs, t.segs.data(), sizeof(DSeg) * t.segs.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&t.d_prefix, sizeof(double) * t.prefix.size()));
-  HIPCHK(hipMemcpy(t.d_prefix, t.prefix.data(), sizeof(double) * t.prefix.size(), hipMemcpyHostToDevice));
-  if (upload_grid(t.bp) < 0 || upload_grid(t.sn) < 0) return -1;
-  if (upload_beams(t) < 0) return -1;
-  HIPCHK(hipMalloc(&t.d_groups, sizeof(float4) * t.groups.size()));
-  HIPCHK(hipMemcpy(t.d_groups, t.groups.data(), sizeof(float4) * t.groups.size(), hipMemcpyHostToDevice));
-  {   // the sensor kernel's wall image (same f32 values it would stage: rad + 0.25 rounded once)
-    std::vector<float4> sw(2 * t.walls.size());
-    for (size_t j = 0; j < t.walls.size(); ++j) {
-      const HWall& w = t.walls[j];
-      sw[2 * j] = make_float4(w.px, w.py, w.rad + 0.25f, w.hx);
-      sw[2 * j + 1] = make_float4(w.qs, w.qc, w.hy, 0.0f);
-    }
-    HIPCHK(hipMalloc(&t.d_swall, sizeof(float4) * sw.size()));
-    HIPCHK(hipMemcpy(t.d_swall, sw.data(), sizeof(float4) * sw.size(), hipMemcpyHostToDevice));
-  }
-  if (getenv("NASCAR_VERBOSE"))
-    fprintf(stderr, "nascar_add_track: %zu walls, %zu groups; broadphase grid %dx%d (%zu entries), sensor grid %dx%d "
-            "(%zu entries, mean %.1f per cell)\n", t.walls.size(), t.groups.size(), t.bp.g.nx, t.bp.g.ny, t.bp.idx.size(),
-            t.sn.g.nx, t.sn.g.ny, t.sn.idx.size(), (double)t.sn.idx.size() / ((double)t.sn.g.nx * t.sn.g.ny));
-  if (getenv("NASCAR_VERBOSE"))
-    fprintf(stderr, "nascar_add_track: beam grid %dx%d (%.2f m cells), %zu cells with lists (%zu dropped: continuation "
-            "offsets), %zu entries (mean %.2f per list), heads %.1f MB + continuations %.1f MB + cell chunks %.1f MB, built in "
-            "%.2f s\n", t.beam.g.nx, t.beam.g.ny, 1.0 / (double)t.beam.g.inv_cell, t.beam.nlist / BEAM_NB,
-            t.beam.dropped, t.beam.entries, (double)t.beam.entries / std::max<size_t>(1, t.beam.nlist),
-            8.0 * t.beam.head.size() / 1e6, 2.0 * t.beam.ent.size() / 1e6, 16.0 * t.beam.chunk.size() / 1e6, t.beam.build_s);
-  t.beam.chunk.clear(); t.beam.ent.clear(); t.beam.head.clear();
-  t.beam.chunk.shrink_to_fit(); t.beam.ent.shrink_to_fit(); t.beam.head.shrink_to_fit();
-  lds_out = sizeof(LWall) * t.walls.size();
-  return 0;
-}
-
-// ------------------------------------------------------------------ track cache on disk (nascar_set_track_cache)
-// A host build (walls, grids and 0.2-0.5 GB of beam lists per track at 1 m cells: ~2 s of 16 threads) written once and read
-// by every later process: ranks of one node (bench.py --gpus N, learn/ppo.py-style SubprocVecEnv runs) share one build
-// per track.  File = magic, format version, the full key (segments, walls, total length, cell size: compared byte for
-// byte on load, so a hash collision can only miss), then the host tables.  Written to a temporary name and renamed; the
-// builders of one key serialise on an flock'ed lock file, so concurrent ranks build each track once and the others load.
-static const uint32_t TRACK_FILE_VERSION = 4;   // 4: 8-byte heads, 16-bit entries, per-track wall bits, chunked cell map
-static std::string g_cache_dir;                       // "" = no disk cache (default)
-static int g_retain = 8;                              // builds kept alive after their last handle (most recent first)
-static std::deque<std::shared_ptr<TrackBuild>>* g_retained = new std::deque<std::shared_ptr<TrackBuild>>();
-// (never destroyed: freeing device memory from a static destructor would run after the HIP runtime's own teardown)
-static void retain_build(const std::shared_ptr<TrackBuild>& tb) {   // (g_track_mu held) most recently used first
-  if (g_retain <= 0) return;
-  auto& R = *g_retained;
-  for (auto it = R.begin(); it != R.end(); ++it)
-    if (*it == tb) { R.erase(it); break; }
-  R.push_front(tb);
-  while ((int)R.size() > g_retain) R.pop_back();
-}
-
-static uint64_t fnv1a64(const std::string& s, uint64_t h) {
-  for (unsigned char c : s) { h ^= c; h *= 0x100000001B3ull; }
-  return h;
-}
-struct Sink {
-  FILE* f; bool ok = true;
-  void raw(const void* p, size_t n) { if (ok && n && fwrite(p, 1, n, f) != n) ok = false; }
-  template <class T> void pod(const T& v) { raw(&v, sizeof v); }
-  template <class T> void vec(const std::vector<T>& v) { const uint64_t n = v.size(); pod(n); raw(v.data(), n * sizeof(T)); }
-};
-struct Source {
-  FILE* f; bool ok = true;
-  void raw(void* p, size_t n) { if (ok && n && fread(p, 1, n, f) != n) ok = false; }
-  template <class T> void pod(T& v) { raw(&v, sizeof v); }
-  template <class T> void vec(std::vector<T>& v) {
-    uint64_t n = 0; pod(n);
-    if (!ok || n > ((uint64_t)1 << 40) / sizeof(T)) { ok = false; return; }
-    v.resize(n); raw(v.data(), n * sizeof(T));
-  }
-};
-template <class IO, class HT> static void track_io(IO& io, HT& t) {   // the host tables, in file order
-  io.vec(t.walls); io.vec(t.segs); io.vec(t.prefix);
-  io.pod(t.total_length); io.pod(t.startline); io.pod(t.has_banking);
-  io.pod(t.bp.g); io.vec(t.bp.start); io.vec(t.bp.idx); io.vec(t.bp.box);
-  io.pod(t.sn.g); io.vec(t.sn.start); io.vec(t.sn.idx); io.vec(t.sn.box);
-  io.pod(t.beam.g); io.vec(t.beam.chunk); io.pod(t.beam.nxc); io.vec(t.beam.ent); io.vec(t.beam.head);
-  io.pod(t.beam.entries); io.pod(t.beam.nlist); io.pod(t.beam.dropped); io.pod(t.beam.build_s);
-  io.vec(t.groups);
-}
-static bool load_track_file(const std::string& path, const std::string& key, HostTrack& t) {
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return false;
-  Source in{f};
-  char magic[8] = {0}; uint32_t ver = 0; std::string k;
-  in.raw(magic, 8); in.pod(ver);
-  std::vector<char> kb; in.vec(kb);
-  bool ok = in.ok && !memcmp(magic, "NASCARTK", 8) && ver == TRACK_FILE_VERSION && kb.size() == key.size() &&
-            !memcmp(kb.data(), key.data(), key.size());
-  if (ok) { track_io(in, t); ok = in.ok; }
-  fclose(f);
-  if (!ok) t = HostTrack();
-  return ok;
-}
-static void save_track_file(const std::string& path, const std::string& key, HostTrack& t) {
-  const std::string tmp = path + ".tmp." + std::to_string((long)getpid());
-  FILE* f = fopen(tmp.c_str(), "wb");
-  if (!f) return;                        // (a cache that cannot be written is only slower)
-  Sink out{f};
-  out.raw("NASCARTK", 8); out.pod(TRACK_FILE_VERSION);
-  std::vector<char> kb(key.begin(), key.end()); out.vec(kb);
-  track_io(out, t);
-  const bool ok = out.ok && fclose(f) == 0;
-  if (ok) rename(tmp.c_str(), path.c_str());
-  else unlink(tmp.c_str());
-}
-// the track's inputs and the beam-list cell size (builds at different cell sizes differ): the disk cache's key
-static std::string track_key(const double* segments, int32_t nseg, double total_length, const double* walls,
-                             int32_t nwall, float beam_cell) {
-  std::string k;
-  const int32_t dims[2] = {nseg, nwall};
-  k.append((const char*)dims, sizeof dims);
-  k.append((const char*)&total_length, sizeof total_length);
-  k.append((const char*)&beam_cell, sizeof beam_cell);
-  k.append((const char*)segments, sizeof(double) * 13 * (size_t)nseg);
-  k.append((const char*)walls, sizeof(double) * 4 * (size_t)nwall);
-  return k;
-}
-// host tables of a track: from the disk cache when it holds this key (*loaded = 1), else built (and written there)
-static int host_track(HostTrack& t, const std::string& key, const double* segments, int32_t nseg, double total_length,
-                      const double* walls, int32_t nwall, float beam_cell, int* loaded) {
-  if (loaded) *loaded = 0;
-  if (g_cache_dir.empty()) return host_build_track(t, segments, nseg, total_length, walls, nwall, beam_cell);
-  char name[64];
-  snprintf(name, sizeof name, "track_%016llx%016llx.nbt", (unsigned long long)fnv1a64(key, 0xCBF29CE484222325ull),
-           (unsigned long long)fnv1a64(key, 0x84222325CBF29CE4ull));
-  const std::string path = g_cache_dir + "/" + name;
-  if (load_track_file(path, key, t)) { if (loaded) *loaded = 1; return 0; }
-  mkdir(g_cache_dir.c_str(), 0777);       // (one level; an existing directory is fine)
-  const int lk = open((path + ".lock").c_str(), O_CREAT | O_RDWR, 0666);
-  if (lk >= 0) flock(lk, LOCK_EX);       // another process may be building this key: wait for it, then load
-  int rc = 0;
-  if (lk >= 0 && load_track_file(path, key, t)) {
-    if (loaded) *loaded = 1;
-  } else {
-    rc = host_build_track(t, segments, nseg, total_length, walls, nwall, beam_cell);
-    if (rc == 0) save_track_file(path, key, t);
-  }
-  if (lk >= 0) { flock(lk, LOCK_UN); close(lk); }
-  return rc;
-}
 // host only (no device): the track's tables into the disk cache -- loaded (returns 1) when a file for this key exists,
 // else built and written (returns 0); a launcher prebuilds a job's tracks once before its ranks start
 extern "C" int nascar_prebuild_track(const double* segments, int32_t nseg, double total_length, const double* walls,
@@ -3795,12 +3250,33 @@ static int apply_pending_tracks(NascarHandle* h, const uint8_t* env_mask, void* 
   return 0;
 }
 
+// prepare()'s buffers grown to hold nt tracks, nb workgroups and nbe env slots of the block map: one too small is
+// replaced by one of the caller's capacity (cap_b workgroups, cap_be env slots; max(nt, 8) tracks).  Earlier launches
+// may still read the old buffers, so they are released after an explicit device synchronisation.
+static int grow_tables(NascarHandle* h, size_t nt, size_t nb, size_t nbe, size_t cap_b, size_t cap_be) {
+  if (nt <= h->cap_tracks && nb <= h->cap_blocks && nbe <= h->cap_blk_env) return 0;
+  HIPCHK(hipDeviceSynchronize());
+  if (nt > h->cap_tracks) {
+    hipFree(h->d_tracks); h->d_tracks = nullptr;
+    const size_t cap = std::max(nt, (size_t)8);
+    HIPCHK(hipMalloc(&h->d_tracks, sizeof(TrackDev) * cap));
+    h->cap_tracks = cap;
+  }
+  if (nb > h->cap_blocks || nbe > h->cap_blk_env) {
+    hipFree(h->d_blk_track); hipFree(h->d_blk_env); h->d_blk_track = h->d_blk_env = nullptr;
+    h->cap_blocks = h->cap_blk_env = 0;
+    HIPCHK(hipMalloc(&h->d_blk_track, sizeof(int) * cap_b));
+    HIPCHK(hipMalloc(&h->d_blk_env, sizeof(int) * cap_be));
+    h->cap_blocks = cap_b; h->cap_blk_env = cap_be;
+  }
+  return 0;
+}
 // Device copies of the track table and the block map, rebuilt when the env -> track assignment changed.
 // Stream-ordered: the tables are uploaded with hipMemcpyAsync on the caller's stream, so the copies land after
 // every earlier launch on that stream (the sharded rollout joins its shard streams into it before returning)
 // and before every later one.  Buffers keep their capacity; only growth (the first call, a newly loaded track)
-// reallocates, and then the old buffers are released after an explicit device synchronisation.  The host
-// source is pinned staging memory owned by the handle, reused only after its previous upload has completed.
+// reallocates (grow_tables).  The host source is the handle's pinned table_stage, reused only after its previous
+// upload has completed (PinnedStage).
 static int prepare(NascarHandle* h, hipStream_t stream) {
   if (h->tracks.empty()) return fail("no track loaded (nascar_add_track)");
   if (!h->dirty_tracks) return 0;
@@ -3819,34 +3295,12 @@ static int prepare(NascarHandle* h, hipStream_t stream) {
   if (h->rt_on) {   // random-track mode: the device builds the map (block_map_kernel) into a fixed grid of nb_cap blocks
     const size_t nt = td.size(), nb = (size_t)(h->E + h->epb - 1) / h->epb + nt;
     if (nt > RT_MAX_TRACKS) return fail("random-track mode supports at most %d loaded tracks", RT_MAX_TRACKS);
-    if (nt > h->cap_tracks || nb > h->cap_blocks || nb * h->epb > h->cap_blk_env) {
-      HIPCHK(hipDeviceSynchronize());
-      if (nt > h->cap_tracks) {
-        hipFree(h->d_tracks); h->d_tracks = nullptr;
-        const size_t cap = std::max(nt, (size_t)8);
-        HIPCHK(hipMalloc(&h->d_tracks, sizeof(TrackDev) * cap));
-        h->cap_tracks = cap;
-      }
-      if (nb > h->cap_blocks || nb * h->epb > h->cap_blk_env) {
-        hipFree(h->d_blk_track); hipFree(h->d_blk_env); h->d_blk_track = h->d_blk_env = nullptr;
-        h->cap_blocks = h->cap_blk_env = 0;
-        HIPCHK(hipMalloc(&h->d_blk_track, sizeof(int) * nb));
-        HIPCHK(hipMalloc(&h->d_blk_env, sizeof(int) * nb * h->epb));
-        h->cap_blocks = nb; h->cap_blk_env = nb * h->epb;
-      }
-    }
+    if (grow_tables(h, nt, nb, nb * h->epb, nb, nb * h->epb)) return -1;   // sized exactly: the grid is fixed
     const size_t b_tr = sizeof(TrackDev) * nt;
-    if (h->ev_stage) HIPCHK(hipEventSynchronize(h->ev_stage));
-    if (b_tr > h->stage_bytes) {
-      if (h->h_stage) hipHostFree(h->h_stage);
-      h->h_stage = nullptr; h->stage_bytes = 0;
-      HIPCHK(hipHostMalloc(&h->h_stage, b_tr));
-      h->stage_bytes = b_tr;
-    }
-    memcpy(h->h_stage, td.data(), b_tr);
-    HIPCHK(hipMemcpyAsync(h->d_tracks, h->h_stage, b_tr, hipMemcpyHostToDevice, stream));
-    if (!h->ev_stage) HIPCHK(hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(h->ev_stage, stream));
+    HIPCHK(h->table_stage.reserve(b_tr));
+    memcpy(h->table_stage.host, td.data(), b_tr);
+    HIPCHK(hipMemcpyAsync(h->d_tracks, h->table_stage.host, b_tr, hipMemcpyHostToDevice, stream));
+    HIPCHK(h->table_stage.record(stream));
     hipLaunchKernelGGL(block_map_kernel, dim3(1), dim3(1024), 0, stream, h->E, h->epb, (int)nt, h->d_rt_env_track,
                        h->d_blk_track, h->d_blk_env, (int)nb, h->d_rt_dirty, 1);
     HIPCHK(hipGetLastError());
@@ -3884,43 +3338,19 @@ static int prepare(NascarHandle* h, hipStream_t stream) {
     }
   }
   const size_t nt = td.size(), nb = blk_track.size();
-  // growth (a new track, a finer layout from nascar_set_envs_per_block): earlier launches may still read the old buffers
-  if (nt > h->cap_tracks || nb > h->cap_blocks || blk_env.size() > h->cap_blk_env) {
-    HIPCHK(hipDeviceSynchronize());
-    if (nt > h->cap_tracks) {
-      hipFree(h->d_tracks); h->d_tracks = nullptr;
-      const size_t cap = std::max(nt, (size_t)8);
-      HIPCHK(hipMalloc(&h->d_tracks, sizeof(TrackDev) * cap));
-      h->cap_tracks = cap;
-    }
-    if (nb > h->cap_blocks || blk_env.size() > h->cap_blk_env) {
-      hipFree(h->d_blk_track); hipFree(h->d_blk_env); h->d_blk_track = h->d_blk_env = nullptr;
-      h->cap_blocks = h->cap_blk_env = 0;
-      const size_t cap = std::max(nb, (size_t)(h->E + h->epb - 1) / h->epb + 8);
-      const size_t cap_env = std::max(blk_env.size(), cap * h->epb);
-      HIPCHK(hipMalloc(&h->d_blk_track, sizeof(int) * cap));
-      HIPCHK(hipMalloc(&h->d_blk_env, sizeof(int) * cap_env));
-      h->cap_blocks = cap; h->cap_blk_env = cap_env;
-    }
-  }
+  // growth (a new track, a finer layout from nascar_set_envs_per_block) leaves 8 workgroups of slack
+  const size_t cap = std::max(nb, (size_t)(h->E + h->epb - 1) / h->epb + 8);
+  if (grow_tables(h, nt, nb, blk_env.size(), cap, std::max(blk_env.size(), cap * h->epb))) return -1;
   const size_t b_tr = sizeof(TrackDev) * nt, b_bt = sizeof(int) * nb, b_be = sizeof(int) * blk_env.size();
-  const size_t need = b_tr + b_bt + b_be;
-  if (h->ev_stage) HIPCHK(hipEventSynchronize(h->ev_stage));   // the previous upload out of the staging buffer
-  if (need > h->stage_bytes) {
-    if (h->h_stage) hipHostFree(h->h_stage);
-    h->h_stage = nullptr; h->stage_bytes = 0;
-    HIPCHK(hipHostMalloc(&h->h_stage, need));
-    h->stage_bytes = need;
-  }
-  char* st = (char*)h->h_stage;
+  HIPCHK(h->table_stage.reserve(b_tr + b_bt + b_be));
+  char* st = (char*)h->table_stage.host;
   memcpy(st, td.data(), b_tr);
   memcpy(st + b_tr, blk_track.data(), b_bt);
   memcpy(st + b_tr + b_bt, blk_env.data(), b_be);
   HIPCHK(hipMemcpyAsync(h->d_tracks, st, b_tr, hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(h->d_blk_track, st + b_tr, b_bt, hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(h->d_blk_env, st + b_tr + b_bt, b_be, hipMemcpyHostToDevice, stream));
-  if (!h->ev_stage) HIPCHK(hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(h->ev_stage, stream));
+  HIPCHK(h->table_stage.record(stream));
   h->nblocks = (int)nb;
   h->map_identity = 1;
   for (size_t s = 0; s < blk_env.size(); ++s)
@@ -4154,6 +3584,13 @@ static int fitness_refused(const NascarHandle* h, int auto_reset) {
   if (h->fit_on && h->rt_on) return fail("fitness accumulation (nascar_set_fitness) is not available in random-track mode");
   return 0;
 }
+// Where a step writes its env flags when the caller passed no buffer: the two readers of a step's flags bring their
+// own, random-track mode's switch after an auto-reset step (rt_after_step) and the fitness accumulators
+// (launch_fitness).  fitness_refused keeps the two apart.
+static uint8_t* step_env_flags(const NascarHandle* h, uint8_t* env_flags, int auto_reset) {
+  if (env_flags) return env_flags;
+  return h->rt_on && auto_reset ? h->d_rt_flags : h->fit_on ? h->d_fit_flags : nullptr;
+}
 // the genome driver's launch for a shard's workgroups [b0, b1) (b0 < 0: the cars [n0, n1) directly)
 static int launch_genome(NascarHandle* h, const Params& P, int b0, int b1, int n0, int n1, uint64_t slots, const float* obs,
                          float* act, hipStream_t s) {
@@ -4173,22 +3610,15 @@ static int step_impl(NascarHandle* h, const void* actions, int32_t discrete, int
   h->pristine = false;
   if (prepare(h, (hipStream_t)stream)) return -1;
   Params P = make_params(h);
-  if (h->fit_on) {
-    uint8_t* ef = env_flags ? env_flags : h->d_fit_flags;
-    if (launch_step_range(h, P, h->nblocks, actions, discrete, policy, seed, step, obs, obs, reward, car_flags, ef, 0,
-                          terminal_obs, (hipStream_t)stream))
-      return -1;
-    return launch_fitness(h, P, 0, h->nblocks, reward, ef, (hipStream_t)stream);
-  }
   // Whole grid on the caller's stream: splitting one step over streams needs a fork and a join per step, and
   // the per-step barrier measured slower than one grid (tools/streams_exp.py: 2 / 4 shards 0.252 / 0.277 ms vs
   // 0.224 ms).  Shards pay off only when they run many steps unsynchronised: the sharded nascar_rollout.
-  const bool rt = h->rt_on && auto_reset;
-  uint8_t* ef = (rt && !env_flags) ? h->d_rt_flags : env_flags;
+  uint8_t* ef = step_env_flags(h, env_flags, auto_reset);
   if (launch_step_range(h, P, h->nblocks, actions, discrete, policy, seed, step, obs, obs, reward, car_flags, ef, auto_reset,
                         terminal_obs, (hipStream_t)stream))
     return -1;
-  return rt ? rt_after_step(h, P, ef, obs, (hipStream_t)stream) : 0;
+  if (h->fit_on && launch_fitness(h, P, 0, h->nblocks, reward, ef, (hipStream_t)stream)) return -1;
+  return h->rt_on && auto_reset ? rt_after_step(h, P, ef, obs, (hipStream_t)stream) : 0;
 }
 extern "C" int nascar_step(NascarHandle* h, const void* actions, int32_t discrete, float* obs, float* reward,
                            uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs, void* stream) {
@@ -4232,13 +3662,55 @@ struct CollectBufs { float* actions; float* logp; float* values; float* timeout_
 enum { AC_SAMPLE = 1, AC_VALUE = 2 };
 static int launch_ac(NascarHandle* h, int what, int c0, int n, uint64_t seed, int64_t step, const float* obs, float* act,
                      float* actions, float* logp, float* values, const uint8_t* tflags, hipStream_t s);
+// Shard s of S: its workgroups [b0, b1) and its cars [c0, c1) -- contiguous because the block map is the identity or
+// there is one shard, which holds every car.  b0 < 0 (nascar_policy_actions): no workgroups, the cars alone.
+struct ShardRange { int b0, b1; size_t c0, c1; };
+static ShardRange shard_range(const NascarHandle* h, int s, int S) {
+  const int b0 = (int)((int64_t)h->nblocks * s / S), b1 = (int)((int64_t)h->nblocks * (s + 1) / S);
+  if (S == 1) return {b0, b1, 0, (size_t)h->N};
+  const size_t E = (size_t)h->E;
+  return {b0, b1, std::min((size_t)b0 * h->epb, E) * h->C, std::min((size_t)b1 * h->epb, E) * h->C};
+}
+// Policies 2 (the SAC actor), 4 (the field of controllers), 5 (genome drivers) and 6 (the sampled actor-critic) produce
+// their actions in launches of their own.  policy_ready: what such a launch needs of the handle and of the buffers it
+// reads obs from and writes act to (null: a buffer of the handle's).
+static int policy_ready(const NascarHandle* h, int policy, const float* obs, const float* act) {
+  if (policy == 2) {
+    if (!h->d_actor) return fail("policy 2 needs an actor (nascar_set_actor)");
+    if (((uintptr_t)obs | (uintptr_t)act) & 7) return fail("actor obs/actions must be 8-byte aligned");
+  }
+  if (policy == 4) {
+    if (!h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
+    if ((uintptr_t)act & 7) return fail("field actions must be 8-byte aligned");
+  }
+  if (policy == 5 && !h->genome_set) return fail("policy 5 needs a genome table (nascar_set_genomes)");
+  if (policy == 6) {
+    if (!h->ac_set) return fail("policy 6 needs an actor-critic (nascar_set_actor_critic)");
+    if ((uintptr_t)act & 7) return fail("actor-critic actions must be 8-byte aligned");
+  }
+  return 0;
+}
+// launch_actions: policy 2, 4, 5 or 6 for the cars of r on stream s, obs ([N][38]) to act ([N][2]).  The genome driver
+// walks r's workgroups in the block map, which need not be the identity, or r's cars where r has no workgroups.
+// Policy 6 with rec (nascar_collect): the step's actions, logp and values records too.
+static int launch_actions(NascarHandle* h, int policy, const Params& P, const ShardRange& r, uint64_t seed, int64_t step,
+                          const float* obs, float* act, const CollectBufs* rec, hipStream_t s) {
+  const int c0 = (int)r.c0, n = (int)(r.c1 - r.c0);
+  if (policy == 6)
+    return launch_ac(h, rec ? AC_SAMPLE | AC_VALUE : AC_SAMPLE, c0, n, seed, step, obs, act, rec ? rec->actions : nullptr,
+                     rec ? rec->logp : nullptr, rec ? rec->values : nullptr, nullptr, s);
+  if (policy == 5) return launch_genome(h, P, r.b0, r.b1, c0, (int)r.c1, ~0ull, obs, act, s);
+  if (policy == 4) return launch_field(h, c0 / h->C, n / h->C, seed, step, obs, act, s);
+  if (n > 0) launch_actor(h, n, obs + r.c0 * 38, act + r.c0 * 2, s);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 // The first n shard streams with their join events, and the fork event, created where missing on the handle's device
 // (whatever is current): a stream and its join event both or neither.  `what` names them in the error.
 static int ensure_shard_streams(NascarHandle* h, int n, const char* what) {
   if ((int)h->sub_stream.size() >= n && h->ev_fork) return 0;
-  int cur = 0;
-  HIPCHK(hipGetDevice(&cur));
-  if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
+  DeviceGuard on(h->cfg.device);
+  HIPCHK(on.err);
   bool ok = true;
   while (ok && (int)h->sub_stream.size() < n) {
     hipStream_t st; hipEvent_t ev;
@@ -4247,7 +3719,6 @@ static int ensure_shard_streams(NascarHandle* h, int n, const char* what) {
     if (ok) { h->sub_stream.push_back(st); h->ev_join.push_back(ev); }
   }
   if (ok && !h->ev_fork) ok = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
-  if (cur != h->cfg.device) hipSetDevice(cur);
   if (!ok) return fail("creating %s failed", what);
   return 0;
 }
@@ -4269,16 +3740,11 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
   S = std::max(1, std::min(S, h->nblocks));
   const bool rt = h->rt_on && auto_reset;
   if (h->rt_on) S = 1;   // random-track mode: the block map changes between steps, so no shard owns a fixed set of envs
-  const bool field = policy == 4, genome = policy == 5;
-  const bool actor = policy == 2 || field || genome || col;   // the actions come from a launch of their own, into d_ro_act
+  // the actions come from a launch of their own (launch_actions; the callers have checked policy_ready), into d_ro_act
+  const bool actor = policy == 2 || policy == 4 || policy == 5 || policy == 6;
   if (actor) {
-    if (col && !h->ac_set) return fail("policy 6 needs an actor-critic (nascar_set_actor_critic)");
     if (col && !h->d_term) HIPCHK(hipMalloc(&h->d_term, sizeof(float) * 38 * (size_t)h->N));
-    if (field && !h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
-    if (genome && !h->genome_set) return fail("policy 5 needs a genome table (nascar_set_genomes)");
-    if (policy == 2 && !h->d_actor) return fail("policy 2 needs an actor (nascar_set_actor)");
-    if (policy == 2 && ((uintptr_t)obs & 7)) return fail("actor obs must be 8-byte aligned");
-    if (!h->map_identity && !genome) S = 1;   // the genome driver walks its shard's env slots of the block map
+    if (!h->map_identity && policy != 5) S = 1;   // the genome driver walks its shard's env slots of the block map
     if (!h->d_ro_act) HIPCHK(hipMalloc(&h->d_ro_act, sizeof(float) * 2 * (size_t)h->N));
   }
   if (S > 1 && ensure_shard_streams(h, S - 1, "the rollout shard streams")) return -1;
@@ -4290,68 +3756,45 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
   }
   const size_t NC = (size_t)h->N, E = (size_t)h->E;
   const bool obs_traj = (traj & NASCAR_TRAJ_OBS) != 0;   // obs = [steps + 1][N][38]: record 0 in, record k + 1 out
-  // the cars of shard s (contiguous: the block map is the identity, or there is one shard)
-  auto shard_cars = [&](int s, size_t& c0, size_t& c1) {
-    const int b0 = (int)((int64_t)h->nblocks * s / S), b1 = (int)((int64_t)h->nblocks * (s + 1) / S);
-    c0 = S == 1 ? 0 : std::min((size_t)b0 * h->epb, E) * h->C;
-    c1 = S == 1 ? NC : std::min((size_t)b1 * h->epb, E) * h->C;
-  };
   auto enqueue = [&]() -> int {
     for (int k = 0; k < steps; ++k) {
       const size_t ko = traj ? (size_t)k : 0;
       float* o_in = obs_traj ? obs + (size_t)k * NC * 38 : obs;
       float* o_out = obs_traj ? obs + (size_t)(k + 1) * NC * 38 : obs;
+      uint8_t* ef = step_env_flags(h, env_flags ? env_flags + ko * E : nullptr, auto_reset);
+      // nascar_collect: a ~ N(mu, std) and V on the step's observation into actions / logp / values [k]; clip(a) drives the step
+      const CollectBufs rec = col ? CollectBufs{col->actions + 2 * ko * NC, col->logp + ko * NC, col->values + ko * NC, nullptr}
+                                  : CollectBufs{};
       // phase-major enqueue (every shard's model launch, then every shard's logic, then sensors): each stream's
       // order is unchanged, but a shard's first launch of the call is queued ~6 us (one launch) after the previous
       // shard's instead of ~18 us (three), so the shards start together
       for (int ph = 0; ph < 3; ++ph) {
         for (int s = 0; s < S; ++s) {
-          const int b0 = (int)((int64_t)h->nblocks * s / S), b1 = (int)((int64_t)h->nblocks * (s + 1) / S);
+          const ShardRange r = shard_range(h, s, S);
           Params P = P0;
-          P.blk0 = b0;
-          if (actor && ph == 0) {
-            const size_t c0 = S == 1 ? 0 : (size_t)b0 * h->epb * h->C;
-            const size_t c1 = S == 1 ? NC : std::min((size_t)b1 * h->epb, E) * h->C;
-            if (col) {   // a ~ N(mu, std) and V on the step's observation: actions / logp / values [k], clip(a) drives the step
-              size_t a0, a1;
-              shard_cars(s, a0, a1);
-              if (launch_ac(h, AC_SAMPLE | AC_VALUE, (int)a0, (int)(a1 - a0), seed, step0 + k, o_in, h->d_ro_act,
-                            col->actions + 2 * ko * NC, col->logp + ko * NC, col->values + ko * NC, nullptr, shard_stream(s)))
-                return -1;
-            } else if (genome) {
-              if (launch_genome(h, P, b0, b1, 0, 0, ~0ull, o_in, h->d_ro_act, shard_stream(s))) return -1;
-            } else if (field) {
-              if (launch_field(h, (int)(c0 / h->C), (int)((c1 - c0) / h->C), seed, step0 + k, o_in, h->d_ro_act, shard_stream(s)))
-                return -1;
-            } else if (c1 > c0) launch_actor(h, (int)(c1 - c0), o_in + c0 * 38, h->d_ro_act + c0 * 2, shard_stream(s));
-            HIPCHK(hipGetLastError());
-          }
-          if (launch_step_range(h, P, b1 - b0, actor ? h->d_ro_act : nullptr, 0, actor ? -1 : policy, seed, step0 + k,
-                                o_in, o_out, reward + ko * NC,
-                                car_flags ? car_flags + ko * NC : nullptr,
-                                env_flags ? env_flags + ko * E : (rt ? h->d_rt_flags : h->fit_on ? h->d_fit_flags : nullptr),
+          P.blk0 = r.b0;
+          if (actor && ph == 0 &&
+              launch_actions(h, policy, P, r, seed, step0 + k, o_in, h->d_ro_act, col ? &rec : nullptr, shard_stream(s)))
+            return -1;
+          if (launch_step_range(h, P, r.b1 - r.b0, actor ? h->d_ro_act : nullptr, 0, actor ? -1 : policy, seed, step0 + k,
+                                o_in, o_out, reward + ko * NC, car_flags ? car_flags + ko * NC : nullptr, ef,
                                 auto_reset, col ? h->d_term : nullptr, shard_stream(s), 1 << ph, ph == 1))
             return -1;
-          if (col && ph == 2) {   // SB3's time-limit bootstrap: V(terminal obs) for the cars of truncated, not terminated envs
-            size_t a0, a1;
-            shard_cars(s, a0, a1);
-            if (launch_ac(h, AC_VALUE, (int)a0, (int)(a1 - a0), seed, step0 + k, h->d_term, nullptr, nullptr, nullptr,
-                          col->timeout_values + ko * NC, env_flags + ko * E, shard_stream(s)))
-              return -1;
-          }
-          if (h->fit_on && ph == 2 &&
-              launch_fitness(h, P, b0, b1, reward + ko * NC, env_flags ? env_flags + ko * E : h->d_fit_flags, shard_stream(s)))
+          // SB3's time-limit bootstrap: V(terminal obs) for the cars of truncated, not terminated envs
+          if (col && ph == 2 &&
+              launch_ac(h, AC_VALUE, (int)r.c0, (int)(r.c1 - r.c0), seed, step0 + k, h->d_term, nullptr, nullptr, nullptr,
+                        col->timeout_values + ko * NC, ef, shard_stream(s)))
             return -1;
+          if (h->fit_on && ph == 2 && launch_fitness(h, P, r.b0, r.b1, reward + ko * NC, ef, shard_stream(s))) return -1;
         }
       }
-      if (rt && rt_after_step(h, P0, env_flags ? env_flags + ko * E : h->d_rt_flags, o_out, stream)) return -1;
+      if (rt && rt_after_step(h, P0, ef, o_out, stream)) return -1;
     }
     if (col)   // values [steps]: V of the observation after the last step, the bootstrap of the last record
       for (int s = 0; s < S; ++s) {
-        size_t a0, a1;
-        shard_cars(s, a0, a1);
-        if (launch_ac(h, AC_VALUE, (int)a0, (int)(a1 - a0), seed, step0 + steps, obs + (size_t)steps * NC * 38, nullptr, nullptr,
-                      nullptr, col->values + (size_t)steps * NC, nullptr, shard_stream(s)))
+        const ShardRange r = shard_range(h, s, S);
+        if (launch_ac(h, AC_VALUE, (int)r.c0, (int)(r.c1 - r.c0), seed, step0 + steps, obs + (size_t)steps * NC * 38, nullptr,
+                      nullptr, nullptr, col->values + (size_t)steps * NC, nullptr, shard_stream(s)))
           return -1;
       }
     return 0;
@@ -4460,8 +3903,7 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
   if (policy == 2 && h->ro_streams == 0) return fail("the fused rollout kernel has no actor (policy 2): use the sharded rollout");
   if (policy == 4 && h->ro_streams == 0)
     return fail("the fused rollout kernel has no controllers (policy 4): use the sharded rollout (rollout streams >= 1)");
-  if (policy == 4 && !h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
-  if (policy == 5 && !h->genome_set) return fail("policy 5 needs a genome table (nascar_set_genomes)");
+  if (policy_ready(h, policy, obs, nullptr)) return -1;   // (the actions go to a buffer of the handle's)
   if (policy == 5 && h->ro_streams == 0)
     return fail("the fused rollout kernel has no genome drivers (policy 5): use the sharded rollout (rollout streams >= 1)");
   if (policy == 5 && h->ro_pipe > 0)
@@ -4505,7 +3947,7 @@ extern "C" int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int
   if (!h || !obs || !reward || !car_flags || !env_flags || !actions || !logp || !values || !timeout_values)
     return fail("null argument");
   if (steps < 1) return fail("collect: steps must be >= 1 (got %d)", steps);
-  if (!h->ac_set) return fail("policy 6 needs an actor-critic (nascar_set_actor_critic)");
+  if (policy_ready(h, 6, obs, nullptr)) return -1;
   if (h->ro_streams == 0)
     return fail("the fused rollout kernel has no actor-critic (policy 6): use the sharded rollout (rollout streams >= 1)");
   if (h->ro_pipe > 0)
@@ -4677,26 +4119,21 @@ extern "C" int nascar_set_genomes(NascarHandle* h, const double* genomes, void* 
   for (size_t i = 0; i < N * 12; ++i)
     if (!std::isfinite(genomes[i]))
       return fail("genome of car %zu: gene %zu is not finite (%g)", i / 12, i % 12, genomes[i]);
-  int cur = 0;
-  HIPCHK(hipGetDevice(&cur));
-  if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
-  hipError_t e = hipSuccess;
-  if (!h->d_genome) e = hipMalloc(&h->d_genome, sizeof(GenomeRec) * N);
-  if (e == hipSuccess && !h->h_genome) e = hipHostMalloc((void**)&h->h_genome, sizeof(GenomeRec) * N);
-  if (e == hipSuccess && !h->ev_genome) e = hipEventCreateWithFlags(&h->ev_genome, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventSynchronize(h->ev_genome);   // the previous upload has left the staging buffer
+  DeviceGuard on(h->cfg.device);
+  hipError_t e = on.err;
+  if (e == hipSuccess && !h->d_genome) e = hipMalloc(&h->d_genome, sizeof(GenomeRec) * N);
+  if (e == hipSuccess) e = h->genome_stage.reserve(sizeof(GenomeRec) * N);
   if (e == hipSuccess) {
+    GenomeRec* st = (GenomeRec*)h->genome_stage.host;
     for (size_t n = 0; n < N; ++n) {
-      GenomeRec& r = h->h_genome[n];
-      memcpy(r.g, genomes + 12 * n, sizeof r.g);
-      r.py_steer = 0; r.pad = 0;
+      memcpy(st[n].g, genomes + 12 * n, sizeof st[n].g);
+      st[n].py_steer = 0; st[n].pad = 0;
     }
-    e = hipMemcpyAsync(h->d_genome, h->h_genome, sizeof(GenomeRec) * N, hipMemcpyHostToDevice, (hipStream_t)stream);
+    e = hipMemcpyAsync(h->d_genome, st, sizeof(GenomeRec) * N, hipMemcpyHostToDevice, (hipStream_t)stream);
   }
-  if (e == hipSuccess) e = hipEventRecord(h->ev_genome, (hipStream_t)stream);
+  if (e == hipSuccess) e = h->genome_stage.record((hipStream_t)stream);
   // a new table is a new set of controllers: GeneticController.__init__ starts each from a zero control_state
   if (e == hipSuccess) e = hipMemsetAsync(h->d_ctl, 0, sizeof(double) * 4 * N, (hipStream_t)stream);
-  if (cur != h->cfg.device) hipSetDevice(cur);
   if (e != hipSuccess) return fail("uploading the genome table failed: %s", hipGetErrorString(e));
   h->genome_set = true;
   return 0;
@@ -4727,26 +4164,10 @@ extern "C" int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t s
   if (!h || !actions) return fail("null argument");
   if (policy < 0 || policy > 6) return fail("unknown policy %d", policy);
   if (policy >= 1 && !obs) return fail("policy %d needs obs", policy);
-  if (policy == 6) {
-    if (!h->ac_set) return fail("policy 6 needs an actor-critic (nascar_set_actor_critic)");
-    if ((uintptr_t)actions & 7) return fail("actor-critic actions must be 8-byte aligned");
-    return launch_ac(h, AC_SAMPLE, 0, h->N, seed, step, obs, actions, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
-  }
-  if (policy == 5) {
-    if (!h->genome_set) return fail("policy 5 needs a genome table (nascar_set_genomes)");
-    return launch_genome(h, make_params(h), -1, 0, 0, h->N, ~0ull, obs, actions, (hipStream_t)stream);
-  }
-  if (policy == 4) {
-    if (!h->field_set) return fail("policy 4 needs a controller table (nascar_set_car_controllers)");
-    if ((uintptr_t)actions & 7) return fail("field actions must be 8-byte aligned");
-    return launch_field(h, 0, h->E, seed, step, obs, actions, (hipStream_t)stream);
-  }
-  if (policy == 2) {
-    if (!h->d_actor) return fail("policy 2 needs an actor (nascar_set_actor)");
-    if (((uintptr_t)obs | (uintptr_t)actions) & 7) return fail("actor obs/actions must be 8-byte aligned");
-    launch_actor(h, h->N, obs, actions, stream);
-    HIPCHK(hipGetLastError());
-    return 0;
+  if (policy == 2 || policy >= 4) {   // the whole batch, by its cars
+    if (policy_ready(h, policy, obs, actions)) return -1;
+    return launch_actions(h, policy, make_params(h), ShardRange{-1, 0, 0, (size_t)h->N}, seed, step, obs, actions, nullptr,
+                          (hipStream_t)stream);
   }
   int nb = (h->N + 255) / 256;
   hipLaunchKernelGGL(policy_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, h->N, policy, seed, step, obs, actions, h->d_ctl);
@@ -4988,12 +4409,10 @@ extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
   const int H1 = m->h1, H2 = m->h2;
   std::vector<float> f(mlp_floats(H1, H2));   // one allocation
   mlp_pack(m, f.data());
-  int cur = 0;
-  HIPCHK(hipGetDevice(&cur));
-  if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
+  DeviceGuard on(h->cfg.device);
   void* d = nullptr;
-  hipError_t e = hipSuccess;
-  if (!h->d_ctrl) e = hipMalloc(&h->d_ctrl, sizeof(MlpDev) * MLP_MAX_CTRL);
+  hipError_t e = on.err;
+  if (e == hipSuccess && !h->d_ctrl) e = hipMalloc(&h->d_ctrl, sizeof(MlpDev) * MLP_MAX_CTRL);
   if (e == hipSuccess) e = hipMalloc(&d, f.size() * 4);
   if (e == hipSuccess) e = hipMemcpy(d, f.data(), f.size() * 4, hipMemcpyHostToDevice);
   MlpDev D{};
@@ -5004,7 +4423,6 @@ extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
     D.h1 = H1; D.h2 = H2; D.activation = m->activation; D.output = m->output;
     e = hipMemcpy(h->d_ctrl + h->ctrl.size(), &D, sizeof(MlpDev), hipMemcpyHostToDevice);
   }
-  if (cur != h->cfg.device) hipSetDevice(cur);
   if (e != hipSuccess) { hipFree(d); return fail("loading the controller failed: %s", hipGetErrorString(e)); }
   h->ctrl.push_back(D);
   h->ctrl_mem.push_back(d);
@@ -5023,24 +4441,14 @@ extern "C" int nascar_update_controller(NascarHandle* h, int32_t id, const Nasca
                 "output %d (load another controller for another shape or kind)", id, D.h1, D.h2, D.activation, D.output,
                 m->h1, m->h2, m->activation, m->output);
   const size_t nf = mlp_floats(D.h1, D.h2);
-  int cur = 0;
-  HIPCHK(hipGetDevice(&cur));
-  if (cur != h->cfg.device) HIPCHK(hipSetDevice(h->cfg.device));
-  hipError_t e = hipSuccess;
-  if (!h->ev_ctrl) e = hipEventCreateWithFlags(&h->ev_ctrl, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventSynchronize(h->ev_ctrl);   // the previous upload has left the staging buffer
-  if (e == hipSuccess && h->ctrl_stage_floats < nf) {
-    if (h->h_ctrl_stage) hipHostFree(h->h_ctrl_stage);
-    h->h_ctrl_stage = nullptr; h->ctrl_stage_floats = 0;
-    e = hipHostMalloc((void**)&h->h_ctrl_stage, 4 * nf);
-    if (e == hipSuccess) h->ctrl_stage_floats = nf;
-  }
+  DeviceGuard on(h->cfg.device);
+  hipError_t e = on.err;
+  if (e == hipSuccess) e = h->ctrl_stage.reserve(4 * nf);
   if (e == hipSuccess) {
-    mlp_pack(m, h->h_ctrl_stage);
-    e = hipMemcpyAsync(h->ctrl_mem[id], h->h_ctrl_stage, 4 * nf, hipMemcpyHostToDevice, (hipStream_t)stream);
+    mlp_pack(m, (float*)h->ctrl_stage.host);
+    e = hipMemcpyAsync(h->ctrl_mem[id], h->ctrl_stage.host, 4 * nf, hipMemcpyHostToDevice, (hipStream_t)stream);
   }
-  if (e == hipSuccess) e = hipEventRecord(h->ev_ctrl, (hipStream_t)stream);
-  if (cur != h->cfg.device) hipSetDevice(cur);
+  if (e == hipSuccess) e = h->ctrl_stage.record((hipStream_t)stream);
   if (e != hipSuccess) return fail("updating controller %d failed: %s", id, hipGetErrorString(e));
   return 0;
 }
@@ -5074,17 +4482,20 @@ extern "C" int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl) 
   h->field_set = true;
   return 0;
 }
-// one launch of the instantiation for (T1, T2, activation); false if there is none (shapes are checked at load)
-static bool mlp_launch(int h1, int h2, int activation, dim3 grid, hipStream_t s, const MlpLaunch& L) {
+// One launch of mlp_field_kernel's instantiation for K's (h1, h2, activation) over a batch of n rows (a wave per 32) and
+// ny grid-y entries (L.slot_id); an error if there is none (shapes are checked at load)
+static int mlp_launch(const MlpDev& K, int n, int ny, hipStream_t s, const MlpLaunch& L) {
+  const dim3 grid(((n + 31) / 32 + AM_WAVES - 1) / AM_WAVES, ny);
 #define X(A, B)                                                                                                  \
-  if (h1 == 32 * (A) && h2 == 32 * (B)) {                                                                        \
-    if (activation == MLP_RELU) hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_RELU>), grid, dim3(64 * AM_WAVES), 0, s, L); \
+  if (K.h1 == 32 * (A) && K.h2 == 32 * (B)) {                                                                    \
+    if (K.activation == MLP_RELU) hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_RELU>), grid, dim3(64 * AM_WAVES), 0, s, L); \
     else hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_TANH>), grid, dim3(64 * AM_WAVES), 0, s, L);              \
-    return true;                                                                                                 \
+    HIPCHK(hipGetLastError());                                                                                   \
+    return 0;                                                                                                    \
   }
   MLP_SHAPES(X)
 #undef X
-  return false;
+  return fail("no kernel for controller shape %d-%d", K.h1, K.h2);
 }
 // The field's actions for envs [env0, env0 + nenv) of obs / act ([E][C][38] / [E][C][2]): one mlp_field_kernel launch
 // per distinct (h1, h2, activation) among the table's controllers (all their slots in the launch's grid y), then one
@@ -5093,7 +4504,6 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
                         hipStream_t s) {
   if (nenv <= 0) return 0;
   const int C = h->C;
-  const int gx = ((nenv + 31) / 32 + AM_WAVES - 1) / AM_WAVES;
   bool done[MLP_MAX_CARS] = {};
   bool builtin = false;
   uint64_t genome_slots = 0;   // slots of NASCAR_CTRL_GENOME: genome_policy_kernel, as policy 5 runs it for those cars
@@ -5112,9 +4522,7 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
       L.slot_id[ns++] = d | (h->field[d] << 8);
       done[d] = true;
     }
-    if (!mlp_launch(K.h1, K.h2, K.activation, dim3(gx, ns), s, L))
-      return fail("no kernel for controller shape %d-%d", K.h1, K.h2);
-    HIPCHK(hipGetLastError());
+    if (mlp_launch(K, nenv, ns, s, L)) return -1;
   }
   const int n0 = env0 * C, n1 = (env0 + nenv) * C;
   if (genome_slots) {
@@ -5144,24 +4552,19 @@ static int launch_ac(NascarHandle* h, int what, int c0, int n, uint64_t seed, in
   L.table = h->d_ctrl; L.obs = obs; L.act = act; L.env0 = c0; L.nenv = n; L.C = 1;
   L.values = values; L.actions = actions; L.logp = logp; L.tflags = tflags; L.tcars = h->C;
   L.log_std[0] = h->ac_log_std[0]; L.log_std[1] = h->ac_log_std[1]; L.seed = seed; L.step = step;
-  const int gx = ((n + 31) / 32 + AM_WAVES - 1) / AM_WAVES;
   const bool both = (what & AC_SAMPLE) && (what & AC_VALUE);
   const bool shared = PI.h1 == VF.h1 && PI.h2 == VF.h2 && PI.activation == VF.activation;
   if (both && shared) {
     L.slot_id[0] = h->ac_pi << 8; L.slot_id[1] = h->ac_vf << 8;
-    if (!mlp_launch(PI.h1, PI.h2, PI.activation, dim3(gx, 2), s, L)) return fail("no kernel for controller shape %d-%d", PI.h1, PI.h2);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return mlp_launch(PI, n, 2, s, L);
   }
   if (what & AC_SAMPLE) {
     L.slot_id[0] = h->ac_pi << 8;
-    if (!mlp_launch(PI.h1, PI.h2, PI.activation, dim3(gx, 1), s, L)) return fail("no kernel for controller shape %d-%d", PI.h1, PI.h2);
-    HIPCHK(hipGetLastError());
+    if (mlp_launch(PI, n, 1, s, L)) return -1;
   }
   if (what & AC_VALUE) {
     L.slot_id[0] = h->ac_vf << 8;
-    if (!mlp_launch(VF.h1, VF.h2, VF.activation, dim3(gx, 1), s, L)) return fail("no kernel for controller shape %d-%d", VF.h1, VF.h2);
-    HIPCHK(hipGetLastError());
+    if (mlp_launch(VF, n, 1, s, L)) return -1;
   }
   return 0;
 }
@@ -5178,10 +4581,7 @@ extern "C" int nascar_controller_forward(NascarHandle* h, int32_t id, const floa
   MlpLaunch L{};   // a flat batch: n envs of one car slot
   L.table = h->d_ctrl; L.obs = obs; L.act = actions; L.env0 = 0; L.nenv = n; L.C = 1;
   L.slot_id[0] = id << 8;
-  if (!mlp_launch(K.h1, K.h2, K.activation, dim3(((n + 31) / 32 + AM_WAVES - 1) / AM_WAVES, 1), (hipStream_t)stream, L))
-    return fail("no kernel for controller shape %d-%d", K.h1, K.h2);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return mlp_launch(K, n, 1, (hipStream_t)stream, L);
 }
 
 extern "C" int nascar_debug_sincosf(const float* x, float* s, float* c, int32_t n, void* stream) {

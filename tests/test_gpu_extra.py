@@ -123,6 +123,29 @@ def test_track_change_waits_for_reset():
         x.close()
 
 
+def test_second_track_added_after_launches():
+    """An engine that has stepped on one track gets a second one (nascar_add_track after launches: the track table
+    is uploaded again, longer, and the block map sorted by track) and moves one env there through a reset; from
+    that reset on it equals, bit for bit, a twin built with both tracks."""
+    from nascargymnasium_amd.batched import BatchedCarEnv
+    E, C = 3, 2
+    tal, mar = os.path.join(TRACKS, "talladega.track"), os.path.join(TRACKS, "martinsville.track")
+    env = BatchedCarEnv(E, C, tal, device="cuda:0")
+    twin = BatchedCarEnv(E, C, [tal, mar, tal], device="cuda:0")
+    env.reset()
+    rng = np.random.default_rng(5)
+    for k in range(60):
+        env.step(torch.from_numpy(_actions(rng, E, C, k)).cuda(), auto_reset=True)
+    env.set_env_tracks([tal, mar, tal])
+    assert torch.equal(env.reset(), twin.reset())
+    for k in range(120):
+        a = torch.from_numpy(_actions(rng, E, C, k)).cuda()
+        env.step(a, auto_reset=True); twin.step(a, auto_reset=True)
+        for f in ("obs", "reward", "car_flags", "env_flags"):
+            assert torch.equal(getattr(env, f).view(torch.uint8), getattr(twin, f).view(torch.uint8)), (k, f)
+    env.close(); twin.close()
+
+
 def env_field(name):
     from nascargymnasium_amd import _lib
     return _lib.INFO_FIELDS.index(name)

@@ -47,6 +47,10 @@ def _bits(a):
     return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
 
 
+def _bits_t(t):
+    return t.view(torch.int32)
+
+
 def test_driver_on_directed_sequences():
     """130 cars (two waves and two lanes: the only block is partial), 64 steps, genomes from the bounds: actions and
     the control state equal the restatement bit for bit at every step"""
@@ -176,6 +180,29 @@ def test_evaluation_rollout_equals_the_host_loop():
     assert np.all(np.isnan(z[:, lt])) and np.all(z[:, da] == -1)
     assert not np.delete(z, [lt, da], axis=1).any()
     a.close(); b.close()
+
+
+def test_back_to_back_genome_uploads_keep_their_order():
+    """Two set_genomes calls with nothing between them share one pinned staging buffer: the second waits for the
+    first upload to leave it, and the table the driver reads is the second one, as in an engine given only that."""
+    E, C = 2, 2
+    rng = np.random.default_rng(7)
+    ga, gb = G.random_genomes(rng, E * C), G.random_genomes(rng, E * C)
+    env, fresh = _engine(E, C, "martinsville"), _engine(E, C, "martinsville")
+    env.reset(); fresh.reset()
+    env.set_genomes(ga)
+    only_a = env.policy_actions(5).clone()
+    env.set_genomes(ga)
+    env.set_genomes(gb)
+    fresh.set_genomes(gb)
+    assert not torch.equal(env.policy_actions(5), only_a)       # the two tables drive differently from the grid
+    fresh.policy_actions(5)
+    for k in range(5):
+        assert torch.equal(_bits_t(env._actions), _bits_t(fresh._actions)), k
+        env.step(env._actions); fresh.step(fresh._actions)
+        env.policy_actions(5); fresh.policy_actions(5)
+    assert np.array_equal(_bits(_ctl(env)), _bits(_ctl(fresh)))
+    env.close(); fresh.close()
 
 
 def test_errors_carry_the_library_message():
