@@ -287,7 +287,10 @@ int nascar_set_state(NascarHandle* h, const void* src_device, void* stream);
  *   policy 6: the sampled actor-critic of nascar_set_actor_critic -- every car draws a ~ N(mu(obs), exp(log_std)^2)
  *             from the Gaussian actor and takes min(max(a, -1), 1), the action SB3's collect_rollouts steps the env with;
  *             the draw is the one of (seed, car, step), see nascar_collect.  Fails without an actor-critic.  actions
- *             8-byte aligned. */
+ *             8-byte aligned.
+ *   policy 7: the explorer of nascar_set_explorer -- the sampled SAC actor, or a deterministic squashed actor with
+ *             exploration noise; returns the action that steps the env.  Fails without an explorer.  actions 8-byte
+ *             aligned. */
 int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, const float* obs,
                           float* actions, void* stream);
 
@@ -346,7 +349,8 @@ int nascar_actor_forward(NascarHandle* h, const float* obs, int32_t n, float* ac
 typedef struct NascarMlp {
     int32_t obs_dim, h1, h2, act_dim;
     int32_t activation;      /* 0 ReLU, 1 Tanh */
-    int32_t output;          /* 0 raw, 1 clip, 2 squash; 3 value (act_dim 1), 4 sampled: nascar_set_actor_critic */
+    int32_t output;          /* 0 raw, 1 clip, 2 squash; 3 value (act_dim 1), 4 sampled: nascar_set_actor_critic;
+                                5 squashed sample (act_dim 4): nascar_set_explorer */
     const float *w1, *b1, *w2, *b2, *w3, *b3;   /* PyTorch layouts, host */
 } NascarMlp;
 #define NASCAR_CTRL_RULE (-1)      /* policy 1 */
@@ -399,6 +403,67 @@ int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps,
                    void* stream);
 int nascar_gae(NascarHandle* h, const float* reward, const float* values, const float* timeout_values,
                const uint8_t* env_flags, int32_t steps, double gamma, double lambda, float* adv, float* ret, void* stream);
+
+/* Off-policy collection: the loop of SB3's off-policy algorithms, as learn/sac.py, learn/td3.py, learn/td3_n.py and
+ * learn/ddpg.py run it (OffPolicyAlgorithm.collect_rollouts, off_policy_algorithm.py: _sample_action, env.step,
+ * _store_transition -> ReplayBuffer.add, then ReplayBuffer.sample for the learner), on the device.
+ * With scale(u) = 2 * ((u + 1) / 2) - 1 (BasePolicy.scale_action: what the replay buffer keeps, SB3's buffer_action) and
+ * unscale(a) = -1 + (0.5 * (a + 1)) * 2 (unscale_action: what steps the env), both float32 for the Box(-1, 1):
+ * Controller output 5 (act_dim 4): SB3's SAC Actor with deterministic = False (sac/policies.py Actor.forward /
+ *   action_log_prob, SquashedDiagGaussianDistribution).  w3 is [4][h2], rows 0-1 actor.mu.weight, rows 2-3
+ *   actor.log_std.weight, b3 [4] likewise.  Per car in float32: mu_j = W3[j].h + b3[j], ls_j = min(max(W3[2 + j].h +
+ *   b3[2 + j], -20), 2) (LOG_STD_MIN / LOG_STD_MAX), g_j = mu_j + expf(ls_j) * eps_j, t_j = tanhf(g_j); the env is stepped
+ *   with u_j = unscale(t_j) and the replay keeps s_j = scale(u_j).  It runs as the explorer only (the field,
+ *   nascar_controller_forward and nascar_set_actor_critic refuse it); nascar_update_controller takes new weights.
+ * Exploration noise on a deterministic actor (TD3 / DDPG with NormalActionNoise, _sample_action; the reference uses
+ *   sigma 0.15 in learn/ddpg.py:93 and 0.75 in learn/td3_n.py:94): an output-2 controller with sigma [2]:
+ *   s_j = min(max(scale(u_det_j) + sigma_j * eps_j, -1), 1), the env is stepped with unscale(s_j), the replay keeps s_j.
+ *   sigma = 0 reproduces the controller's output-2 action bit for bit.
+ * eps is the Box-Muller pair of nascar_collect's draw (same formula, same counter key of (seed, car, step)) with the salts
+ *   0x4F46465F504F4C31 (u0) and 0x7F4A7C15D1B54A33 (u1), used by no other action source: it depends on (seed, car index,
+ *   step) alone, never on the shard, tile or lane that computes it.
+ * nascar_set_explorer: policy 7 of nascar_policy_actions (which returns u, the action that steps the env; actions 8-byte
+ *   aligned) and source 7 of nascar_collect_transitions.  id: an output-5 controller (sigma must be NULL) or an output-2
+ *   controller with sigma [2] (host, finite, >= 0; NULL = zeros); id < 0 clears it.  nascar_step_driven and nascar_rollout
+ *   refuse policy 7 (use nascar_collect_transitions).
+ * NascarReplay: caller-owned device buffers, `capacity` step slots of N = E * C cars: 319 bytes per transition (2 x 152
+ *   obs, 8 action, 4 reward, 3 flag bytes), i.e. 319 * N bytes per step slot.  obs, next_obs and actions 8-byte aligned.
+ * nascar_collect_transitions: `steps` x (source on the current obs + CarEnv.step with auto-reset) on the sharded rollout,
+ *   no host synchronisation; step k writes slot (pos + k) % capacity (a call may wrap the ring any number of times):
+ *     obs       the observation the action was computed on
+ *     actions   s, the scaled buffer action
+ *     reward    the step's reward
+ *     done      terminated | truncated of the car's env
+ *     timeout   truncated & !terminated (TimeLimit.truncated under handle_timeout_termination)
+ *     next_obs  the terminal observation for the cars of done envs, else the new observation (_store_transition)
+ *     live      1 unless the car was already disabled before the step (car flag bit 0 without bit 1): a learner masks
+ *               dead cars with it (the reference trains at 1 car, where it is always 1)
+ *   source: 7 the explorer, or 0 the uniform policy (SB3's learning_starts warm-up, action_space.sample(): policy 0's
+ *   draw u, stored as scale(u)).  obs [N][38] is in/out (8-byte aligned): the current observation on entry, the last
+ *   step's on return; pos in [0, capacity).  Identical, bit for bit, to `steps` x (nascar_policy_actions(source) +
+ *   nascar_step(auto_reset, terminal_obs)) with the buffer assembled on the host.  Each shard writes its own cars' rows
+ *   after its sensor launch (one small kernel; no batch-wide staging copy beyond nascar_collect's terminal observations).
+ *   Fails with rollout streams 0, under nascar_set_rollout_pipe and with fitness accumulation on, as nascar_collect does;
+ *   random-track mode and envs that do not sit in one track's workgroups in order run as one shard.
+ * nascar_replay_sample: ReplayBuffer.sample (buffers.py _get_samples) as one launch, uniform over `size` filled step
+ *   slots x N cars.  Sample i of (seed, draw): key = the counter key of (seed, car = i, step = draw),
+ *     slot = ((uint64)mix32(key ^ 0x5245504C5F534C54) * size) >> 32,  car = ((uint64)mix32(key ^ 0x2545F4914F6CDD1D) * N) >> 32
+ *   gathered into contiguous outputs obs / next_obs [batch][38], actions [batch][2], reward [batch], done [batch] float32 =
+ *   done * (1 - timeout) (what SB3 hands the learner), live [batch] uint8.  batch = 0 launches nothing; size < 1,
+ *   size > capacity and batch < 0 are errors.  obs / next_obs / actions outputs 8-byte aligned. */
+typedef struct NascarReplay {
+    float *obs, *next_obs;            /* [capacity][N][38] */
+    float *actions;                   /* [capacity][N][2]   the scaled buffer action s */
+    float *reward;                    /* [capacity][N] */
+    uint8_t *done, *timeout, *live;   /* [capacity][N] */
+    int32_t capacity;
+} NascarReplay;
+int nascar_set_explorer(NascarHandle* h, int32_t id, const float* sigma);
+int nascar_collect_transitions(NascarHandle* h, int32_t source, uint64_t seed, int64_t step0, int32_t steps, float* obs,
+                               const NascarReplay* replay, int32_t pos, void* stream);
+int nascar_replay_sample(NascarHandle* h, const NascarReplay* replay, int32_t size, uint64_t seed, int64_t draw,
+                         int32_t batch, float* obs, float* next_obs, float* actions, float* reward, float* done,
+                         uint8_t* live, void* stream);
 
 /* Genome drivers: the rule driver of the reference's genetic trainer (game/control/genetic_controller.py,
  * learn/genetic_trainer.py), one genome per car.  GeneticController.control cannot run as written (its line 81 reads an

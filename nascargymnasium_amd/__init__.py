@@ -9,7 +9,7 @@ one fused HIP kernel for gfx950 over E envs x C cars (libnascar.so, include/nasc
 from .track import Track, available_tracks, build_walls, load_track, track_path  # noqa: F401
 
 __all__ = ["Track", "available_tracks", "build_walls", "load_track", "track_path", "BatchedCarEnv", "CarEnv",
-           "BaseEnv", "VecCarEnv", "RolloutBatch", "ActorCriticNet"]
+           "BaseEnv", "VecCarEnv", "RolloutBatch", "ActorCriticNet", "ReplayBuffer", "ReplaySamples", "SquashedActorNet"]
 
 
 def __getattr__(name):   # torch-dependent pieces load lazily
@@ -25,4 +25,7 @@ def __getattr__(name):   # torch-dependent pieces load lazily
     if name in ("RolloutBatch", "ActorCriticNet"):
         from . import onpolicy
         return getattr(onpolicy, name)
+    if name in ("ReplayBuffer", "ReplaySamples", "SquashedActorNet"):
+        from . import offpolicy
+        return getattr(offpolicy, name)
     raise AttributeError(name)

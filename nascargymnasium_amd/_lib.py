@@ -48,6 +48,12 @@ N_FITNESS = len(FITNESS_FIELDS)
 N_GENES = 12
 
 
+class NascarReplay(ctypes.Structure):
+    """include/nascar.h NascarReplay: the caller-owned device ring of nascar_collect_transitions / nascar_replay_sample."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("obs", "next_obs", "actions", "reward", "done", "timeout", "live")] + \
+               [("capacity", ctypes.c_int32)]
+
+
 class NascarConfig(ctypes.Structure):
     _fields_ = [("num_envs", ctypes.c_int32), ("num_cars", ctypes.c_int32), ("reset_on_lap", ctypes.c_int32),
                 ("device", ctypes.c_int32), ("start_x", ctypes.c_double), ("start_y", ctypes.c_double),
@@ -159,6 +165,12 @@ def lib():
     L.nascar_collect.restype = ctypes.c_int
     L.nascar_gae.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_double, ctypes.c_double, vp, vp, vp]
     L.nascar_gae.restype = ctypes.c_int
+    L.nascar_set_explorer.argtypes = [vp, i32, fp]
+    L.nascar_set_explorer.restype = ctypes.c_int
+    L.nascar_collect_transitions.argtypes = [vp, i32, u64, i64, i32, vp, ctypes.POINTER(NascarReplay), i32, vp]
+    L.nascar_collect_transitions.restype = ctypes.c_int
+    L.nascar_replay_sample.argtypes = [vp, ctypes.POINTER(NascarReplay), i32, u64, i64, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.nascar_replay_sample.restype = ctypes.c_int
     L.nascar_set_genomes.argtypes = [vp, d_p, vp]
     L.nascar_set_genomes.restype = ctypes.c_int
     L.nascar_set_fitness.argtypes = [vp, i32, vp]
@@ -209,6 +221,7 @@ EXPORTED = ["nascar_create", "nascar_destroy", "nascar_last_error", "nascar_add_
             "nascar_check_controller", "nascar_add_controller", "nascar_controller_forward", "nascar_set_car_controllers",
             "nascar_set_genomes", "nascar_set_fitness", "nascar_get_fitness",
             "nascar_update_controller", "nascar_set_actor_critic", "nascar_collect", "nascar_gae",
+            "nascar_set_explorer", "nascar_collect_transitions", "nascar_replay_sample",
             "nascar_debug_sincosf", "nascar_debug_f64math", "nascar_debug_toi", "nascar_debug_collide", "nascar_debug_car_contact", "nascar_debug_sensors", "nascar_track_draw", "nascar_set_random_tracks",
             "nascar_get_env_tracks", "nascar_vec_post", "nascar_check_actions", "nascar_set_track_cache",
             "nascar_prebuild_track", "nascar_debug_block_map"]

@@ -581,11 +581,71 @@ class BatchedCarEnv:
                                          float(gamma), float(gae_lambda), _ptr(adv), _ptr(ret), _stream()))
         return adv, ret
 
+    # ------------------------------------------------------------------ off-policy collection (policy 7)
+    def set_explorer(self, actor_or_controller=None, sigma=None):
+        """The exploring action source of SB3's off-policy algorithms (policy 7 of policy_actions, source 7 of
+        collect_transitions): a nascargymnasium_amd.policy.SquashedActor (load_sb3_sac_actor, random_squashed_actor,
+        SquashedActorNet.export) -- SAC's actor sampled, a = tanh(mu + exp(log_std) * eps) -- or an OUT_SQUASH Controller
+        with `sigma` = (s0, s1) >= 0, TD3 / DDPG's NormalActionNoise on the deterministic action, clipped to the Box
+        (sigma None = zeros: the controller's own action).  Takes one of the handle's 16 controller ids; `update_explorer`
+        replaces weights and sigma without taking more.  None clears it."""
+        from .policy import OUT_SQUASH, OUT_SQUASH_SAMPLE
+        if actor_or_controller is None:
+            _lib.check(self.L.nascar_set_explorer(self.h, -1, None))
+            self._explorer = None
+            return
+        a = actor_or_controller
+        if a.output not in (OUT_SQUASH, OUT_SQUASH_SAMPLE):
+            raise ValueError(f"the explorer is a SquashedActor or an OUT_SQUASH Controller, not output {a.output}")
+        if a.output == OUT_SQUASH_SAMPLE and sigma is not None:
+            raise ValueError("a SquashedActor samples from its own log_std head: it takes no noise sigma")
+        m, _keep = _lib.mlp_struct(a)
+        with torch.cuda.device(self.device):
+            cid = _lib.check(self.L.nascar_add_controller(self.h, ctypes.byref(m)))
+        self._explorer = (cid, int(a.output))
+        self._set_explorer_sigma(sigma)
+
+    def _set_explorer_sigma(self, sigma):
+        s = None if sigma is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, np.float32), (2,)))
+        _lib.check(self.L.nascar_set_explorer(self.h, self._explorer[0],
+                                              None if s is None else s.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+
+    def update_explorer(self, actor_or_controller=None, sigma=None):
+        """New weights of the same shape, activation and kind into the loaded explorer, ordered on the current stream (a
+        learner's per-iteration update), and / or a new noise sigma; takes no controller id."""
+        if getattr(self, "_explorer", None) is None:
+            raise RuntimeError("update_explorer: no explorer loaded (set_explorer first)")
+        if actor_or_controller is not None:
+            m, _keep = _lib.mlp_struct(actor_or_controller)
+            with torch.cuda.device(self.device):
+                _lib.check(self.L.nascar_update_controller(self.h, self._explorer[0], ctypes.byref(m), _stream()))
+        if sigma is not None:
+            self._set_explorer_sigma(sigma)
+
+    def collect_transitions(self, replay, steps: int, seed: int = 0, step0: int = 0, source: int = 7):
+        """`steps` steps of SB3's OffPolicyAlgorithm.collect_rollouts on the device: per step the explorer (source 7) or
+        the uniform policy (source 0: the learning_starts warm-up) acts on the current observation, the envs step with
+        auto-reset, and the transition -- obs, next_obs (the terminal observation where the env ended), the scaled action,
+        reward, done, timeout, live -- goes into slot (replay.pos + k) % capacity of `replay`
+        (nascargymnasium_amd.offpolicy.ReplayBuffer), whose pos / size advance.  Runs on the sharded rollout's streams, no
+        host synchronisation; equals `steps` x (policy_actions(source, seed, step0 + k) + step(auto_reset=True,
+        terminal_obs=True)) with the buffer filled on the host.  Returns the observation after the last step."""
+        K = int(steps)
+        if replay.E != self.E or replay.C != self.C or replay.device != self.device:
+            raise ValueError("the replay buffer belongs to another env shape or device")
+        with torch.cuda.device(self.device):
+            r = replay.struct()
+            _lib.check(self.L.nascar_collect_transitions(self.h, int(source), int(seed), int(step0), K, _ptr(self.obs),
+                                                         ctypes.byref(r), int(replay.pos), _stream()))
+        replay.advance(K)
+        return self.obs
+
     def policy_actions(self, policy: int, seed: int = 0, step: int = 0, obs: Optional[torch.Tensor] = None):
         """device-generated actions: 0 uniform U[-1,1]^2, 1 BaseController fallback driver, 2 the SAC actor, 3 the noisy
         rule driver, 4 the field of per-car controllers (set_car_controllers), 5 the genome drivers (set_genomes: the
         rule driver with per-car evolved constants; shares the rule driver's per-car state), 6 the sampled actor-critic
-        (set_actor_critic): clip(a, -1, 1) of the draw a ~ N(mu(obs), exp(log_std)) of (seed, car, step)."""
+        (set_actor_critic): clip(a, -1, 1) of the draw a ~ N(mu(obs), exp(log_std)) of (seed, car, step), 7 the explorer
+        (set_explorer): the sampled SAC actor, or a squashed actor with exploration noise -- the action that steps the env."""
         o = self.obs if obs is None else obs
         with torch.cuda.device(self.device):
             _lib.check(self.L.nascar_policy_actions(self.h, int(policy), int(seed), int(step), _ptr(o),

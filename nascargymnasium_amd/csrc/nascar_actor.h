@@ -330,6 +330,8 @@ actor_mfma32_kernel(int N, const float* __restrict__ obs, float* __restrict__ ac
 //               MLP_OUT_VALUE  a critic: w3 is the value head padded to [2][h2] (second row zero); m0 + b3[0] goes to
 //                              values[row] (4-byte stores), nothing to act
 //               MLP_OUT_SAMPLE the Gaussian actor of SB3's on-policy algorithms, sampled: see mlp_sample below
+//               MLP_OUT_SQUASH_SAMPLE  SB3's SAC actor, sampled (a four-row head: mu and log_std): see mlp_explore below;
+//                              only the explorer's instantiations (EXPL) hold it
 // Shapes: obs_dim 38 and act_dim 2; (h1, h2) one of MLP_SHAPES below -- 256-256 (the SAC checkpoints), 64-64 (ppo_789,
 // ppo_849), 256-128 (a2c_best_model3), and 128-128, 256-32, 32-256 for other nets; every other shape is rejected when the
 // controller is loaded (mlp_shape_ok), with a message naming it.  That includes TD3's SB3 default [400, 300]: no multiple
@@ -349,15 +351,15 @@ actor_mfma32_kernel(int N, const float* __restrict__ obs, float* __restrict__ ac
 #define MLP_MAX_CTRL 16    // controllers per handle
 #define MLP_MAX_CARS 64    // car slots per env (nascar_create's limit)
 enum { MLP_RELU = 0, MLP_TANH = 1 };
-enum { MLP_OUT_RAW = 0, MLP_OUT_CLIP = 1, MLP_OUT_SQUASH = 2, MLP_OUT_VALUE = 3, MLP_OUT_SAMPLE = 4 };
+enum { MLP_OUT_RAW = 0, MLP_OUT_CLIP = 1, MLP_OUT_SQUASH = 2, MLP_OUT_VALUE = 3, MLP_OUT_SAMPLE = 4, MLP_OUT_SQUASH_SAMPLE = 5 };
 #define MLP_SHAPES(X) X(8, 8) X(8, 4) X(8, 1) X(4, 4) X(2, 2) X(1, 8)
 struct MlpDev {        // one loaded controller (device pointers)
   const float* w1t;    // [38][h1]  W1 transposed
   const float* b1;     // [h1]
   const float* w2t;    // [h1][h2]  W2 transposed
   const float* b2;     // [h2]
-  const float* w3;     // [2][h2]
-  const float* b3;     // [2]
+  const float* w3;     // [2][h2]; MLP_OUT_SQUASH_SAMPLE: [4][h2], rows 0-1 mu.weight, rows 2-3 log_std.weight
+  const float* b3;     // [2]; MLP_OUT_SQUASH_SAMPLE: [4]
   int h1, h2, activation, output;
 };
 struct MlpLaunch {
@@ -368,11 +370,12 @@ struct MlpLaunch {
   int slot_id[MLP_MAX_CARS];   // blockIdx.y -> car slot c | controller id << 8
   // the on-policy outputs (nascar_collect, policy 6); rows are indexed like act, by car
   float* values;               // MLP_OUT_VALUE: [E][C]
-  float* actions;              // MLP_OUT_SAMPLE: the unclipped action [E][C][2] (null: not kept)
+  float* actions;              // MLP_OUT_SAMPLE: the unclipped action [E][C][2] (null: not kept); the explorer (EXPL):
+                               //   the scaled buffer action s [E][C][2] (null: not kept)
   float* logp;                 // MLP_OUT_SAMPLE: [E][C] (null: not kept)
   const uint8_t* tflags;       // non-null: env_flags [E] of the step; only the cars of truncated, not terminated envs
   int tcars;                   //   are computed (env = car / tcars), and a tile or workgroup without one returns at once
-  float log_std[2];
+  float log_std[2];            // MLP_OUT_SAMPLE; the explorer on an MLP_OUT_SQUASH controller: the noise sigma [2]
   uint64_t seed;
   int64_t step;
 };
@@ -423,10 +426,47 @@ __device__ __forceinline__ f32x2 mlp_out(float mu0, float mu1) {
   }
   return (f32x2){mu0, mu1};
 }
-template <int T1, int T2, int ACT>
+// The explorer (policy 7, nascar_set_explorer): the two exploring epilogues of SB3's off-policy algorithms, on the
+// Box-Muller pair of mlp_sample with salts of their own (EXPLORE_SALT0 / EXPLORE_SALT1, include/nascar.h) -- the draw
+// depends on (seed, car, step) alone.  With scale(u) = 2 * ((u + 1) / 2) - 1 (scale_action, what the replay buffer keeps)
+// and unscale(a) = -1 + (0.5 * (a + 1)) * 2 (unscale_action, what steps the env; mlp_out<MLP_OUT_SQUASH>'s expression):
+//   MLP_OUT_SQUASH_SAMPLE  SquashedDiagGaussianDistribution, SAC's Actor with deterministic = False: m2 / m3 are the
+//     log_std rows, ls = min(max(ls, -20), 2), g = mu + expf(ls) * eps, u = unscale(tanhf(g)), s = scale(u)
+//   MLP_OUT_SQUASH with sigma  NormalActionNoise on a deterministic actor (TD3 / DDPG, OffPolicyAlgorithm._sample_action):
+//     s = min(max(scale(u_det) + sigma * eps, -1), 1), u = unscale(s); sigma = 0 gives u_det back bit for bit
+//     (scale and unscale are exact on an unscale's result)
+#define EXPLORE_SALT0 0x4F46465F504F4C31ull
+#define EXPLORE_SALT1 0x7F4A7C15D1B54A33ull
+#define REPLAY_SALT_SLOT 0x5245504C5F534C54ull
+#define REPLAY_SALT_CAR 0x2545F4914F6CDD1Dull
+__device__ __forceinline__ float scale_action(float u) { return 2.0f * ((u + 1.0f) / 2.0f) - 1.0f; }
+__device__ __forceinline__ float unscale_action(float a) { return -1.0f + ((0.5f * (a + 1.0f)) * 2.0f); }
+__device__ __forceinline__ void mlp_explore(const MlpLaunch& L, const MlpDev& W, size_t car, float m0, float m1, float m2,
+                                            float m3, f32x2& u, f32x2& s) {
+  const uint64_t key = policy_key(L.seed, L.step, car);
+  const float u0 = (float)((mix32(key ^ EXPLORE_SALT0) >> 8) + 1u) * (1.0f / 16777216.0f);
+  const float u1 = (float)(mix32(key ^ EXPLORE_SALT1) >> 8) * (1.0f / 16777216.0f);
+  const float r = sqrtf(-2.0f * logf(u0)), th = 6.283185307179586f * u1;
+  const float e0 = r * cosf(th), e1 = r * sinf(th);
+  const float mu0 = m0 + W.b3[0], mu1 = m1 + W.b3[1];
+  if (W.output == MLP_OUT_SQUASH_SAMPLE) {   // wave-uniform
+    const float l0 = fminf(fmaxf(m2 + W.b3[2], -20.0f), 2.0f), l1 = fminf(fmaxf(m3 + W.b3[3], -20.0f), 2.0f);
+    const float g0 = mu0 + expf(l0) * e0, g1 = mu1 + expf(l1) * e1;
+    u = (f32x2){unscale_action(tanhf(g0)), unscale_action(tanhf(g1))};
+    s = (f32x2){scale_action(u.x), scale_action(u.y)};
+  } else {
+    const f32x2 d = mlp_out<MLP_OUT_SQUASH>(mu0, mu1);
+    s = (f32x2){fminf(fmaxf(scale_action(d.x) + L.log_std[0] * e0, -1.0f), 1.0f),
+                fminf(fmaxf(scale_action(d.y) + L.log_std[1] * e1, -1.0f), 1.0f)};
+    u = (f32x2){unscale_action(s.x), unscale_action(s.y)};
+  }
+}
+// EXPL: the explorer's instantiations (policy 7), separate so that the others compile to what they were: a four-row w3 in
+// LDS and four layer-3 sums (rows 2-3 zero for a two-row controller), and mlp_explore as the only epilogue.
+template <int T1, int T2, int ACT, bool EXPL = false>
 __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
   constexpr int H1 = 32 * T1, H2 = 32 * T2;
-  __shared__ float s_b1[H1], s_b2[H2], s_w3[2 * H2];
+  __shared__ float s_b1[H1], s_b2[H2], s_w3[(EXPL ? 4 : 2) * H2];
   const int c = L.slot_id[blockIdx.y] & 255;
   bool wanted = true;
   if (L.tflags) {   // timeout values: only the cars of envs that were truncated and not terminated at this step
@@ -441,7 +481,12 @@ __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
   const MlpDev W = L.table[L.slot_id[blockIdx.y] >> 8];
   for (int i = threadIdx.x; i < H1; i += 64 * AM_WAVES) s_b1[i] = W.b1[i];
   for (int i = threadIdx.x; i < H2; i += 64 * AM_WAVES) s_b2[i] = W.b2[i];
-  for (int i = threadIdx.x; i < 2 * H2; i += 64 * AM_WAVES) s_w3[i] = W.w3[i];
+  if (EXPL) {
+    const int n3 = (W.output == MLP_OUT_SQUASH_SAMPLE ? 4 : 2) * H2;
+    for (int i = threadIdx.x; i < 4 * H2; i += 64 * AM_WAVES) s_w3[i] = i < n3 ? W.w3[i] : 0.0f;
+  } else {
+    for (int i = threadIdx.x; i < 2 * H2; i += 64 * AM_WAVES) s_w3[i] = W.w3[i];
+  }
   __syncthreads();
   const int l = threadIdx.x & 63, r = l & 31, h = l >> 5;
   const int tile = blockIdx.x * AM_WAVES + (threadIdx.x >> 6);
@@ -482,7 +527,7 @@ __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
       for (int o = 0; o < T2; ++o) acc[o] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[32 * o], b, acc[o], 0, 0, 0);
     }
   // layer 3: partial sums over this lane's half of the hidden units, then the two halves of the observation added
-  float m0 = 0.0f, m1 = 0.0f;
+  float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
 #pragma unroll
   for (int t = 0; t < T2; ++t)
 #pragma unroll
@@ -491,9 +536,24 @@ __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
       const float v = mlp_act<ACT>(acc[t][q] + s_b2[u]);
       m0 = fmaf(s_w3[u], v, m0);
       m1 = fmaf(s_w3[H2 + u], v, m1);
+      if (EXPL) {
+        m2 = fmaf(s_w3[2 * H2 + u], v, m2);
+        m3 = fmaf(s_w3[3 * H2 + u], v, m3);
+      }
     }
   m0 += __shfl_xor(m0, 32);
   m1 += __shfl_xor(m1, 32);
+  if (EXPL) {
+    m2 += __shfl_xor(m2, 32);
+    m3 += __shfl_xor(m3, 32);
+    if (h == 0 && i < L.nenv) {
+      f32x2 u, s;
+      mlp_explore(L, W, car, m0, m1, m2, m3, u, s);
+      *(f32x2*)&L.act[2 * car] = u;
+      if (L.actions) *(f32x2*)&L.actions[2 * car] = s;
+    }
+    return;
+  }
   if (h == 0 && i < L.nenv) {
     const float mu0 = m0 + W.b3[0], mu1 = m1 + W.b3[1];
     f32x2* out = (f32x2*)&L.act[2 * car];

@@ -1498,6 +1498,8 @@ __global__ void field_policy_kernel(int n0, int n1, int C, FieldCodes F, uint64_
   act[2 * n] = a0; act[2 * n + 1] = a1;
 }
 
+#include "nascar_replay.h"   // the off-policy collection's ring kernels (they take policy 0's draw from policy_car)
+
 // Genome driver (policy 5, NASCAR_CTRL_GENOME): BaseController._fallback_control with its constants replaced by the
 // car's 12 genes -- GeneticController.control (game/control/genetic_controller.py:64-119) without its lines 81-82,
 // which cannot run (line 81 reads an attribute that is defined nowhere).  Gene order: GeneticController.default_genome;
@@ -2957,6 +2959,10 @@ struct NascarHandle {
   bool ac_set = false; int ac_pi = -1, ac_vf = -1; float ac_log_std[2] = {0.0f, 0.0f};
   float* d_term = nullptr;
   PinnedStage ctrl_stage;
+  // the explorer (policy 7, nascar_collect_transitions): its controller (output MLP_OUT_SQUASH_SAMPLE, or MLP_OUT_SQUASH
+  // with the noise sigma), and the car / env flags [N] / [E] of the step a transition is assembled from (one allocation)
+  int ex_id = -1; float ex_sigma[2] = {0.0f, 0.0f};
+  uint8_t* d_rp_cf = nullptr; uint8_t* d_rp_ef = nullptr;
   // genome drivers (policy 5, NASCAR_CTRL_GENOME): the per-car gene records, outside the state arena; their upload is
   // staged in pinned memory and ordered on the caller's stream
   GenomeRec* d_genome = nullptr; bool genome_set = false;
@@ -3135,6 +3141,7 @@ extern "C" void nascar_destroy(NascarHandle* h) {
   for (void* p : h->ctrl_mem) hipFree(p);
   hipFree(h->d_ctrl);
   hipFree(h->d_term);
+  hipFree(h->d_rp_cf);   // (d_rp_ef is its tail)
   hipFree(h->d_rt);
   hipFree(h->d_genome);
   hipFree(h->d_fit);
@@ -3638,6 +3645,9 @@ extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed
   if (policy == 6)
     return fail("driven step: policy 6 (the sampled actor-critic) runs in launches of its own -- use nascar_policy_actions + "
                 "nascar_step or nascar_collect");
+  if (policy == 7)
+    return fail("driven step: policy 7 (the explorer) runs in a launch of its own -- use nascar_policy_actions + nascar_step "
+                "or nascar_collect_transitions");
   if (policy != 0 && policy != 1 && policy != 3) return fail("driven step policy must be 0, 1 or 3 (got %d)", policy);
   return step_impl(h, nullptr, 0, policy, seed, step, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
 }
@@ -3662,6 +3672,11 @@ struct CollectBufs { float* actions; float* logp; float* values; float* timeout_
 enum { AC_SAMPLE = 1, AC_VALUE = 2 };
 static int launch_ac(NascarHandle* h, int what, int c0, int n, uint64_t seed, int64_t step, const float* obs, float* act,
                      float* actions, float* logp, float* values, const uint8_t* tflags, hipStream_t s);
+// the explorer (policy 7) on the cars [c0, c0 + n): u to act, the scaled buffer action s to s_out (null: not kept)
+static int launch_explorer(NascarHandle* h, int c0, int n, uint64_t seed, int64_t step, const float* obs, float* act,
+                           float* s_out, hipStream_t s);
+// the ring of nascar_collect_transitions (the sharded rollout fills slot (pos + k) % capacity at step k) and its source
+struct ReplayRun { NascarReplay R; int pos, source; };
 // Shard s of S: its workgroups [b0, b1) and its cars [c0, c1) -- contiguous because the block map is the identity or
 // there is one shard, which holds every car.  b0 < 0 (nascar_policy_actions): no workgroups, the cars alone.
 struct ShardRange { int b0, b1; size_t c0, c1; };
@@ -3688,6 +3703,10 @@ static int policy_ready(const NascarHandle* h, int policy, const float* obs, con
     if (!h->ac_set) return fail("policy 6 needs an actor-critic (nascar_set_actor_critic)");
     if ((uintptr_t)act & 7) return fail("actor-critic actions must be 8-byte aligned");
   }
+  if (policy == 7) {
+    if (h->ex_id < 0) return fail("policy 7 needs an explorer (nascar_set_explorer)");
+    if ((uintptr_t)act & 7) return fail("explorer actions must be 8-byte aligned");
+  }
   return 0;
 }
 // launch_actions: policy 2, 4, 5 or 6 for the cars of r on stream s, obs ([N][38]) to act ([N][2]).  The genome driver
@@ -3696,6 +3715,7 @@ static int policy_ready(const NascarHandle* h, int policy, const float* obs, con
 static int launch_actions(NascarHandle* h, int policy, const Params& P, const ShardRange& r, uint64_t seed, int64_t step,
                           const float* obs, float* act, const CollectBufs* rec, hipStream_t s) {
   const int c0 = (int)r.c0, n = (int)(r.c1 - r.c0);
+  if (policy == 7) return launch_explorer(h, c0, n, seed, step, obs, act, rec ? rec->actions : nullptr, s);
   if (policy == 6)
     return launch_ac(h, rec ? AC_SAMPLE | AC_VALUE : AC_SAMPLE, c0, n, seed, step, obs, act, rec ? rec->actions : nullptr,
                      rec ? rec->logp : nullptr, rec ? rec->values : nullptr, nullptr, s);
@@ -3736,12 +3756,20 @@ static int upload_params(NascarHandle* h, const Params& P, hipStream_t stream) {
 }
 static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed, int64_t step0, int32_t steps, float* obs,
                            float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, int32_t traj,
-                           hipStream_t stream, const CollectBufs* col = nullptr) {
+                           hipStream_t stream, const CollectBufs* col = nullptr, const ReplayRun* rp = nullptr) {
   S = std::max(1, std::min(S, h->nblocks));
   const bool rt = h->rt_on && auto_reset;
   if (h->rt_on) S = 1;   // random-track mode: the block map changes between steps, so no shard owns a fixed set of envs
   // the actions come from a launch of their own (launch_actions; the callers have checked policy_ready), into d_ro_act
-  const bool actor = policy == 2 || policy == 4 || policy == 5 || policy == 6;
+  const bool actor = policy == 2 || policy == 4 || policy == 5 || policy == 6 || policy == 7;
+  if (rp) {   // nascar_collect_transitions: a shard's cars must be contiguous, whatever the source
+    if (!h->map_identity) S = 1;
+    if (!h->d_term) HIPCHK(hipMalloc(&h->d_term, sizeof(float) * 38 * (size_t)h->N));
+    if (!h->d_rp_cf) {
+      HIPCHK(hipMalloc(&h->d_rp_cf, (size_t)h->N + (size_t)h->E));
+      h->d_rp_ef = h->d_rp_cf + h->N;
+    }
+  }
   if (actor) {
     if (col && !h->d_term) HIPCHK(hipMalloc(&h->d_term, sizeof(float) * 38 * (size_t)h->N));
     if (!h->map_identity && policy != 5) S = 1;   // the genome driver walks its shard's env slots of the block map
@@ -3761,7 +3789,28 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
       const size_t ko = traj ? (size_t)k : 0;
       float* o_in = obs_traj ? obs + (size_t)k * NC * 38 : obs;
       float* o_out = obs_traj ? obs + (size_t)(k + 1) * NC * 38 : obs;
-      uint8_t* ef = step_env_flags(h, env_flags ? env_flags + ko * E : nullptr, auto_reset);
+      uint8_t* ef = rp ? h->d_rp_ef : step_env_flags(h, env_flags ? env_flags + ko * E : nullptr, auto_reset);
+      // nascar_collect_transitions: the step runs in place on obs and writes its reward into the ring's slot; the
+      // explorer writes the slot's scaled action beside the action that steps the envs
+      const size_t slot = rp ? (size_t)((rp->pos + (int64_t)k) % rp->R.capacity) : 0;
+      const size_t slot1 = rp ? (slot + 1) % (size_t)rp->R.capacity : 0;
+      float* rew_k = rp ? rp->R.reward + slot * NC : reward + ko * NC;
+      uint8_t* cf_k = rp ? h->d_rp_cf : car_flags ? car_flags + ko * NC : nullptr;
+      float* term_k = col || rp ? h->d_term : nullptr;
+      const CollectBufs rrec = rp ? CollectBufs{rp->R.actions + 2 * slot * NC, nullptr, nullptr, nullptr} : CollectBufs{};
+      // one transition of shard range r, after its sensors (random-track mode: after the track switch)
+      auto store = [&](const ShardRange& r, hipStream_t st) -> int {
+        const long long lanes = (long long)(r.c1 - r.c0) * RP_ROW;
+        if (lanes <= 0) return 0;
+        hipLaunchKernelGGL(replay_store_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, (int)r.c0, (int)r.c1,
+                           h->C, (const float*)o_out, (const float*)h->d_term, (const uint8_t*)h->d_rp_cf,
+                           (const uint8_t*)h->d_rp_ef, rp->R.next_obs + slot * NC * 38,
+                           k + 1 < steps ? rp->R.obs + slot1 * NC * 38 : nullptr, rp->R.done + slot * NC,
+                           rp->R.timeout + slot * NC, rp->R.live + slot * NC, rp->R.actions + 2 * slot * NC, rp->source, seed,
+                           step0 + k);
+        HIPCHK(hipGetLastError());
+        return 0;
+      };
       // nascar_collect: a ~ N(mu, std) and V on the step's observation into actions / logp / values [k]; clip(a) drives the step
       const CollectBufs rec = col ? CollectBufs{col->actions + 2 * ko * NC, col->logp + ko * NC, col->values + ko * NC, nullptr}
                                   : CollectBufs{};
@@ -3773,13 +3822,17 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
           const ShardRange r = shard_range(h, s, S);
           Params P = P0;
           P.blk0 = r.b0;
+          if (rp && k == 0 && ph == 0 && r.c1 > r.c0)   // the first slot's obs rows: the observation on entry
+            HIPCHK(hipMemcpyAsync(rp->R.obs + (slot * NC + r.c0) * 38, obs + r.c0 * 38, sizeof(float) * 38 * (r.c1 - r.c0),
+                                  hipMemcpyDeviceToDevice, shard_stream(s)));
           if (actor && ph == 0 &&
-              launch_actions(h, policy, P, r, seed, step0 + k, o_in, h->d_ro_act, col ? &rec : nullptr, shard_stream(s)))
+              launch_actions(h, policy, P, r, seed, step0 + k, o_in, h->d_ro_act, col ? &rec : rp ? &rrec : nullptr,
+                             shard_stream(s)))
             return -1;
           if (launch_step_range(h, P, r.b1 - r.b0, actor ? h->d_ro_act : nullptr, 0, actor ? -1 : policy, seed, step0 + k,
-                                o_in, o_out, reward + ko * NC, car_flags ? car_flags + ko * NC : nullptr, ef,
-                                auto_reset, col ? h->d_term : nullptr, shard_stream(s), 1 << ph, ph == 1))
+                                o_in, o_out, rew_k, cf_k, ef, auto_reset, term_k, shard_stream(s), 1 << ph, ph == 1))
             return -1;
+          if (rp && ph == 2 && !rt && store(r, shard_stream(s))) return -1;
           // SB3's time-limit bootstrap: V(terminal obs) for the cars of truncated, not terminated envs
           if (col && ph == 2 &&
               launch_ac(h, AC_VALUE, (int)r.c0, (int)(r.c1 - r.c0), seed, step0 + k, h->d_term, nullptr, nullptr, nullptr,
@@ -3789,6 +3842,7 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
         }
       }
       if (rt && rt_after_step(h, P0, ef, o_out, stream)) return -1;
+      if (rp && rt && store(shard_range(h, 0, 1), stream)) return -1;
     }
     if (col)   // values [steps]: V of the observation after the last step, the bootstrap of the last record
       for (int s = 0; s < S; ++s) {
@@ -3899,6 +3953,7 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
                               void* stream) {
   if (!h || !obs || !reward) return fail("null argument");
   if (policy == 6) return fail("policy 6 (the sampled actor-critic) fills a learner's buffers: use nascar_collect");
+  if (policy == 7) return fail("policy 7 (the explorer) fills a learner's replay ring: use nascar_collect_transitions");
   if (policy < 0 || policy > 5) return fail("rollout policy must be 0, 1, 2, 3, 4 or 5 (got %d)", policy);
   if (policy == 2 && h->ro_streams == 0) return fail("the fused rollout kernel has no actor (policy 2): use the sharded rollout");
   if (policy == 4 && h->ro_streams == 0)
@@ -3962,6 +4017,61 @@ extern "C" int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int
   const CollectBufs col{actions, logp, values, timeout_values};
   return rollout_sharded(h, h->ro_streams, 6, seed, step0, steps, obs, reward, car_flags, env_flags, 1,
                          NASCAR_TRAJ_RECORDS | NASCAR_TRAJ_OBS, (hipStream_t)stream, &col);
+}
+// Off-policy collection (include/nascar.h): `steps` x (source 7 or 0 on the current obs + CarEnv.step with auto-reset) on
+// the sharded rollout, every step's transition written into the caller's ring by the shard that stepped it
+static int replay_check(const NascarHandle* h, const NascarReplay* R, const char* what) {
+  if (!R || !R->obs || !R->next_obs || !R->actions || !R->reward || !R->done || !R->timeout || !R->live)
+    return fail("%s: null replay buffer", what);
+  if (R->capacity < 1) return fail("%s: replay capacity must be >= 1 (got %d)", what, R->capacity);
+  if (((uintptr_t)R->obs | (uintptr_t)R->next_obs | (uintptr_t)R->actions) & 7)
+    return fail("%s: replay obs / next_obs / actions must be 8-byte aligned", what);
+  if ((uintptr_t)R->reward & 3) return fail("%s: replay reward must be 4-byte aligned", what);
+  (void)h;
+  return 0;
+}
+extern "C" int nascar_collect_transitions(NascarHandle* h, int32_t source, uint64_t seed, int64_t step0, int32_t steps,
+                                          float* obs, const NascarReplay* replay, int32_t pos, void* stream) {
+  if (!h || !obs) return fail("null argument");
+  if (replay_check(h, replay, "collect_transitions")) return -1;
+  if (source != 0 && source != 7)
+    return fail("collect_transitions: source must be 7 (the explorer) or 0 (uniform warm-up), got %d", source);
+  if (steps < 1) return fail("collect_transitions: steps must be >= 1 (got %d)", steps);
+  if (pos < 0 || pos >= replay->capacity)
+    return fail("collect_transitions: pos %d outside [0, capacity = %d)", pos, replay->capacity);
+  if (source == 7 && policy_ready(h, 7, obs, nullptr)) return -1;
+  if (h->ro_streams == 0)
+    return fail("the fused rollout kernel fills no replay ring: use the sharded rollout (rollout streams >= 1)");
+  if (h->ro_pipe > 0)
+    return fail("the pipelined rollout fills no replay ring: switch it off (nascar_set_rollout_pipe(h, 0))");
+  if (h->fit_on)
+    return fail("collect_transitions steps with auto-reset: switch fitness accumulation off (nascar_set_fitness(h, 0))");
+  if ((uintptr_t)obs & 7) return fail("collect_transitions obs must be 8-byte aligned");
+  if (vis_refused(h)) return -1;
+  h->pristine = false;
+  if (prepare(h, (hipStream_t)stream)) return -1;
+  const ReplayRun rp{*replay, pos, source};
+  return rollout_sharded(h, h->ro_streams, source, seed, step0, steps, obs, nullptr, nullptr, nullptr, 1, 0,
+                         (hipStream_t)stream, nullptr, &rp);
+}
+extern "C" int nascar_replay_sample(NascarHandle* h, const NascarReplay* replay, int32_t size, uint64_t seed, int64_t draw,
+                                    int32_t batch, float* obs, float* next_obs, float* actions, float* reward, float* done,
+                                    uint8_t* live, void* stream) {
+  if (!h) return fail("null argument");
+  if (replay_check(h, replay, "replay_sample")) return -1;
+  if (size < 1 || size > replay->capacity)
+    return fail("replay_sample: size %d outside [1, capacity = %d] (the filled step slots)", size, replay->capacity);
+  if (batch < 0) return fail("replay_sample: batch must be >= 0 (got %d)", batch);
+  if (batch == 0) return 0;
+  if (!obs || !next_obs || !actions || !reward || !done || !live) return fail("replay_sample: null output buffer");
+  if (((uintptr_t)obs | (uintptr_t)next_obs | (uintptr_t)actions) & 7)
+    return fail("replay_sample: obs / next_obs / actions outputs must be 8-byte aligned");
+  if (((uintptr_t)reward | (uintptr_t)done) & 3) return fail("replay_sample: reward / done outputs must be 4-byte aligned");
+  const ReplayDev R{replay->obs, replay->next_obs, replay->actions, replay->reward, replay->done, replay->timeout, replay->live};
+  hipLaunchKernelGGL(replay_sample_kernel, dim3((batch + 7) / 8), dim3(256), 0, (hipStream_t)stream, R, h->N, size, seed, draw,
+                     batch, obs, next_obs, actions, reward, done, live);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 extern "C" int nascar_gae(NascarHandle* h, const float* reward, const float* values, const float* timeout_values,
                           const uint8_t* env_flags, int32_t steps, double gamma, double lambda, float* adv, float* ret,
@@ -4162,7 +4272,7 @@ extern "C" int nascar_get_fitness(NascarHandle* h, double* out, void* stream) {
 extern "C" int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, const float* obs,
                                      float* actions, void* stream) {
   if (!h || !actions) return fail("null argument");
-  if (policy < 0 || policy > 6) return fail("unknown policy %d", policy);
+  if (policy < 0 || policy > 7) return fail("unknown policy %d", policy);
   if (policy >= 1 && !obs) return fail("policy %d needs obs", policy);
   if (policy == 2 || policy >= 4) {   // the whole batch, by its cars
     if (policy_ready(h, policy, obs, actions)) return -1;
@@ -4370,35 +4480,43 @@ static bool mlp_shape_ok(int h1, int h2) {
 extern "C" int nascar_check_controller(const NascarMlp* m) {
   if (!m) return fail("null argument");
   const bool value = m->act_dim == 1 && m->output == MLP_OUT_VALUE;   // a critic: one output, the value
-  if (m->obs_dim != ACT_OBS || (m->act_dim != ACT_OUT && !value) || !mlp_shape_ok(m->h1, m->h2))
+  const bool head4 = m->act_dim == 4 && m->output == MLP_OUT_SQUASH_SAMPLE;   // the sampled SAC actor: mu and log_std rows
+  if (m->obs_dim != ACT_OBS || (m->act_dim != ACT_OUT && !value && !head4) || !mlp_shape_ok(m->h1, m->h2))
     return fail("controller shape %d -> %d -> %d -> %d unsupported: need obs 38, 2 actions and hidden layers 256-256, 256-128, "
                 "256-32, 128-128, 64-64 or 32-256 (the SB3 checkpoints the reference ships; TD3's [400, 300] is not among them)",
                 m->obs_dim, m->h1, m->h2, m->act_dim);
   if (m->activation != MLP_RELU && m->activation != MLP_TANH)
     return fail("controller activation must be 0 (ReLU) or 1 (Tanh), got %d", m->activation);
   if (m->output == MLP_OUT_VALUE && !value) return fail("controller output 3 (value) needs act_dim 1, got %d", m->act_dim);
+  if (m->output == MLP_OUT_SQUASH_SAMPLE && !head4)
+    return fail("controller output 5 (squashed sample) needs act_dim 4 (w3 rows: mu, then log_std), got %d", m->act_dim);
   if (m->output != MLP_OUT_RAW && m->output != MLP_OUT_CLIP && m->output != MLP_OUT_SQUASH && m->output != MLP_OUT_VALUE &&
-      m->output != MLP_OUT_SAMPLE)
-    return fail("controller output must be 0 (raw), 1 (clip), 2 (squash), 3 (value, act_dim 1) or 4 (sampled), got %d", m->output);
+      m->output != MLP_OUT_SAMPLE && m->output != MLP_OUT_SQUASH_SAMPLE)
+    return fail("controller output must be 0 (raw), 1 (clip), 2 (squash), 3 (value, act_dim 1), 4 (sampled) or 5 (squashed "
+                "sample, act_dim 4), got %d", m->output);
   return 0;
 }
 // A controller's device image in host floats: W1^T [38][h1], b1, W2^T [h1][h2], b2, W3 [2][h2], b3 [2] (the transposes
 // give mlp_field_kernel's A operands coalesced rows); a critic's value head is padded with a zero second row
-static size_t mlp_floats(int H1, int H2) { return (size_t)ACT_OBS * H1 + H1 + (size_t)H1 * H2 + H2 + 2 * (size_t)H2 + 2; }
+// (the sampled SAC actor's head has four rows: rows3 = 4)
+static int mlp_rows3(int output) { return output == MLP_OUT_SQUASH_SAMPLE ? 4 : 2; }
+static size_t mlp_floats(int H1, int H2, int rows3) {
+  return (size_t)ACT_OBS * H1 + H1 + (size_t)H1 * H2 + H2 + rows3 * (size_t)H2 + rows3;
+}
 static void mlp_pack(const NascarMlp* m, float* p) {
-  const int H1 = m->h1, H2 = m->h2, A = m->act_dim;
+  const int H1 = m->h1, H2 = m->h2, A = m->act_dim, R3 = mlp_rows3(m->output);
   float* w1t = p; p += (size_t)ACT_OBS * H1;
   float* b1 = p; p += H1;
   float* w2t = p; p += (size_t)H1 * H2;
   float* b2 = p; p += H2;
-  float* w3 = p; p += 2 * (size_t)H2;
+  float* w3 = p; p += R3 * (size_t)H2;
   float* b3 = p;
   for (int o = 0; o < H1; ++o)
     for (int i = 0; i < ACT_OBS; ++i) w1t[(size_t)i * H1 + o] = m->w1[(size_t)o * ACT_OBS + i];
   for (int o = 0; o < H2; ++o)
     for (int i = 0; i < H1; ++i) w2t[(size_t)i * H2 + o] = m->w2[(size_t)o * H1 + i];
   memcpy(b1, m->b1, 4 * (size_t)H1); memcpy(b2, m->b2, 4 * (size_t)H2);
-  memset(w3, 0, 8 * (size_t)H2); b3[0] = b3[1] = 0.0f;
+  memset(w3, 0, 4 * R3 * (size_t)H2); memset(b3, 0, 4 * (size_t)R3);
   memcpy(w3, m->w3, 4 * (size_t)A * H2); memcpy(b3, m->b3, 4 * (size_t)A);
 }
 extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
@@ -4407,7 +4525,7 @@ extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
   if (!m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3) return fail("null controller weights");
   if ((int)h->ctrl.size() >= MLP_MAX_CTRL) return fail("at most %d controllers per handle", MLP_MAX_CTRL);
   const int H1 = m->h1, H2 = m->h2;
-  std::vector<float> f(mlp_floats(H1, H2));   // one allocation
+  std::vector<float> f(mlp_floats(H1, H2, mlp_rows3(m->output)));   // one allocation
   mlp_pack(m, f.data());
   DeviceGuard on(h->cfg.device);
   void* d = nullptr;
@@ -4419,7 +4537,7 @@ extern "C" int nascar_add_controller(NascarHandle* h, const NascarMlp* m) {
   if (e == hipSuccess) {
     const float* d32 = (const float*)d;
     D.w1t = d32; D.b1 = D.w1t + (size_t)ACT_OBS * H1; D.w2t = D.b1 + H1;
-    D.b2 = D.w2t + (size_t)H1 * H2; D.w3 = D.b2 + H2; D.b3 = D.w3 + 2 * (size_t)H2;
+    D.b2 = D.w2t + (size_t)H1 * H2; D.w3 = D.b2 + H2; D.b3 = D.w3 + mlp_rows3(m->output) * (size_t)H2;
     D.h1 = H1; D.h2 = H2; D.activation = m->activation; D.output = m->output;
     e = hipMemcpy(h->d_ctrl + h->ctrl.size(), &D, sizeof(MlpDev), hipMemcpyHostToDevice);
   }
@@ -4440,7 +4558,7 @@ extern "C" int nascar_update_controller(NascarHandle* h, int32_t id, const Nasca
     return fail("update of controller %d: it is %d-%d, activation %d, output %d; the new weights are %d-%d, activation %d, "
                 "output %d (load another controller for another shape or kind)", id, D.h1, D.h2, D.activation, D.output,
                 m->h1, m->h2, m->activation, m->output);
-  const size_t nf = mlp_floats(D.h1, D.h2);
+  const size_t nf = mlp_floats(D.h1, D.h2, mlp_rows3(D.output));
   DeviceGuard on(h->cfg.device);
   hipError_t e = on.err;
   if (e == hipSuccess) e = h->ctrl_stage.reserve(4 * nf);
@@ -4471,8 +4589,8 @@ extern "C" int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl) 
   if (!ctrl) { h->field_set = false; return 0; }
   for (int c = 0; c < h->C; ++c)
     if (ctrl[c] >= 0 && ctrl[c] < (int)h->ctrl.size() && h->ctrl[ctrl[c]].output >= MLP_OUT_VALUE)
-      return fail("car slot %d: controller %d is a critic or a sampled actor (nascar_set_actor_critic), no driver of the field",
-                  c, ctrl[c]);
+      return fail("car slot %d: controller %d is a critic or a sampled actor (nascar_set_actor_critic, nascar_set_explorer), "
+                  "no driver of the field", c, ctrl[c]);
   for (int c = 0; c < h->C; ++c)
     if (ctrl[c] < NASCAR_CTRL_GENOME || (ctrl[c] == NASCAR_CTRL_GENOME && !h->genome_set) || ctrl[c] >= (int)h->ctrl.size())
       return fail("car slot %d: unknown controller id %d (%d loaded with nascar_add_controller; built-in sources are -1 rule, "
@@ -4484,11 +4602,15 @@ extern "C" int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl) 
 }
 // One launch of mlp_field_kernel's instantiation for K's (h1, h2, activation) over a batch of n rows (a wave per 32) and
 // ny grid-y entries (L.slot_id); an error if there is none (shapes are checked at load)
-static int mlp_launch(const MlpDev& K, int n, int ny, hipStream_t s, const MlpLaunch& L) {
+// explore: the explorer's instantiations (policy 7: the exploring epilogues, a four-row head)
+static int mlp_launch(const MlpDev& K, int n, int ny, hipStream_t s, const MlpLaunch& L, bool explore = false) {
   const dim3 grid(((n + 31) / 32 + AM_WAVES - 1) / AM_WAVES, ny);
 #define X(A, B)                                                                                                  \
   if (K.h1 == 32 * (A) && K.h2 == 32 * (B)) {                                                                    \
-    if (K.activation == MLP_RELU) hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_RELU>), grid, dim3(64 * AM_WAVES), 0, s, L); \
+    if (explore && K.activation == MLP_RELU)                                                                     \
+      hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_RELU, true>), grid, dim3(64 * AM_WAVES), 0, s, L);           \
+    else if (explore) hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_TANH, true>), grid, dim3(64 * AM_WAVES), 0, s, L); \
+    else if (K.activation == MLP_RELU) hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_RELU>), grid, dim3(64 * AM_WAVES), 0, s, L); \
     else hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_TANH>), grid, dim3(64 * AM_WAVES), 0, s, L);              \
     HIPCHK(hipGetLastError());                                                                                   \
     return 0;                                                                                                    \
@@ -4568,12 +4690,41 @@ static int launch_ac(NascarHandle* h, int what, int c0, int n, uint64_t seed, in
   }
   return 0;
 }
+// The explorer of nascar_set_explorer on the cars [c0, c0 + n) of obs ([N][38], a flat batch as launch_ac's): the action
+// that steps the env to act, the scaled buffer action to s_out (null: not kept); the draw is (seed, car, step)'s
+static int launch_explorer(NascarHandle* h, int c0, int n, uint64_t seed, int64_t step, const float* obs, float* act,
+                           float* s_out, hipStream_t s) {
+  if (n <= 0) return 0;
+  const MlpDev& K = h->ctrl[h->ex_id];
+  MlpLaunch L{};
+  L.table = h->d_ctrl; L.obs = obs; L.act = act; L.env0 = c0; L.nenv = n; L.C = 1;
+  L.actions = s_out; L.log_std[0] = h->ex_sigma[0]; L.log_std[1] = h->ex_sigma[1]; L.seed = seed; L.step = step;
+  L.slot_id[0] = h->ex_id << 8;
+  return mlp_launch(K, n, 1, s, L, true);
+}
+extern "C" int nascar_set_explorer(NascarHandle* h, int32_t id, const float* sigma) {
+  if (!h) return fail("null argument");
+  if (id < 0) { h->ex_id = -1; return 0; }
+  if (id >= (int)h->ctrl.size()) return fail("explorer: unknown controller id %d (%d loaded with nascar_add_controller)", id, (int)h->ctrl.size());
+  const int out = h->ctrl[id].output;
+  if (out != MLP_OUT_SQUASH_SAMPLE && out != MLP_OUT_SQUASH)
+    return fail("explorer: controller %d has output %d; need 5 (the sampled SAC actor) or 2 (squash, with a noise sigma)", id, out);
+  if (out == MLP_OUT_SQUASH_SAMPLE && sigma)
+    return fail("explorer: controller %d is a sampled SAC actor (output 5): it takes no noise sigma (pass NULL)", id);
+  float s0 = 0.0f, s1 = 0.0f;
+  if (sigma) { s0 = sigma[0]; s1 = sigma[1]; }
+  if (!std::isfinite(s0) || !std::isfinite(s1) || s0 < 0.0f || s1 < 0.0f)
+    return fail("explorer: sigma (%g, %g) must be finite and >= 0", s0, s1);
+  h->ex_id = id; h->ex_sigma[0] = s0; h->ex_sigma[1] = s1;
+  return 0;
+}
 extern "C" int nascar_controller_forward(NascarHandle* h, int32_t id, const float* obs, int32_t n, float* actions,
                                          void* stream) {
   if (!h || n < 0) return fail("bad argument");
   if (id < 0 || id >= (int)h->ctrl.size()) return fail("unknown controller id %d (%d loaded)", id, (int)h->ctrl.size());
   if (h->ctrl[id].output >= MLP_OUT_VALUE)
-    return fail("controller %d is a critic or a sampled actor: it runs as policy 6 (nascar_set_actor_critic)", id);
+    return fail("controller %d is a critic or a sampled actor: it runs as policy 6 (nascar_set_actor_critic) or 7 "
+                "(nascar_set_explorer)", id);
   if (n == 0) return 0;   // an empty batch has no buffers: its pointers may be null
   if (!obs || !actions) return fail("bad argument");
   if ((uintptr_t)actions & 7) return fail("controller actions must be 8-byte aligned");

@@ -281,3 +281,98 @@ def mlp_forward_numpy(ctrl: Controller, obs, dtype=np.float64, output=None):
     if out == OUT_SQUASH:
         return dt(-1) + (dt(0.5) * (np.tanh(mu) + dt(1))) * dt(2)
     return mu
+
+
+# ------------------------------------------------------------------ the sampled SAC actor (policy 7, collect_transitions)
+OUT_SQUASH_SAMPLE = 5                    # NascarMlp.output: SB3's SAC Actor with deterministic=False (act_dim 4)
+LOG_STD_KEYS = ("actor.log_std.weight", "actor.log_std.bias")
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0    # stable_baselines3/sac/policies.py
+
+
+class SquashedActor(NamedTuple):
+    """SB3's SAC actor with its log_std head: a Controller whose w3 is [4, h2] -- rows 0-1 actor.mu.weight, rows 2-3
+    actor.log_std.weight -- and b3 [4] likewise.  output is OUT_SQUASH_SAMPLE: a = tanh(mu + exp(clip(log_std, -20, 2)) *
+    eps), then unscale_action; BatchedCarEnv.set_explorer / collect_transitions."""
+    w1: np.ndarray
+    b1: np.ndarray
+    w2: np.ndarray
+    b2: np.ndarray
+    w3: np.ndarray
+    b3: np.ndarray
+    h1: int
+    h2: int
+    activation: int
+    kind: str = "sac"
+
+    output = OUT_SQUASH_SAMPLE
+
+    @property
+    def arrays(self):
+        return (self.w1, self.b1, self.w2, self.b2, self.w3, self.b3)
+
+    def deterministic(self) -> Controller:
+        """the mean branch alone: the OUT_SQUASH Controller load_sb3_policy reads from the same checkpoint"""
+        return Controller(self.w1, self.b1, self.w2, self.b2, np.ascontiguousarray(self.w3[:2]),
+                          np.ascontiguousarray(self.b3[:2]), self.h1, self.h2, self.activation, OUT_SQUASH, self.kind)
+
+
+def make_squashed_actor(arrays, activation: int = RELU, kind: str = "random") -> SquashedActor:
+    """A SquashedActor from six arrays (PyTorch layouts; w3 [4, h2], b3 [4]), checked for a 38 -> h1 -> h2 -> 4 shape."""
+    w1, b1, w2, b2, w3, b3 = [np.ascontiguousarray(np.asarray(a, np.float32)) for a in arrays]
+    if w1.ndim != 2 or w2.ndim != 2 or w3.ndim != 2:
+        raise ValueError("squashed actor weights must be 2-D")
+    h1, h2 = int(w1.shape[0]), int(w2.shape[0])
+    want = ((h1, 38), (h1,), (h2, h1), (h2,), (4, h2), (4,))
+    got = tuple(a.shape for a in (w1, b1, w2, b2, w3, b3))
+    if got != want:
+        raise ValueError(f"squashed actor shapes {got}, expected {want} (obs 38 -> h1 -> h2 -> mu [2] + log_std [2])")
+    if activation not in (RELU, TANH):
+        raise ValueError(f"activation {activation} unknown")
+    return SquashedActor(w1, b1, w2, b2, w3, b3, h1, h2, int(activation), kind)
+
+
+def load_sb3_sac_actor(zip_path: str) -> SquashedActor:
+    """The stochastic actor of an SB3 SAC checkpoint zip: ``actor.latent_pi.*``, ``actor.mu.*`` and ``actor.log_std.*``
+    (the head load_sb3_actor leaves out), ReLU as SAC's MlpPolicy.  ``policy.pth`` is read with
+    torch.load(weights_only=True): nothing is unpickled.  A ``use_sde`` checkpoint (its log_std is a [h2, 2] parameter,
+    not a layer) and an actor-critic (PPO / A2C) zip raise ValueError."""
+    import torch
+    with zipfile.ZipFile(zip_path) as z:
+        sd = torch.load(io.BytesIO(z.read("policy.pth")), weights_only=True, map_location="cpu")
+    if "actor.log_std" in sd or any(k.startswith("actor.") and "sde" in k for k in sd):
+        raise ValueError(f"{zip_path}: a use_sde SAC checkpoint (state-dependent exploration) is not supported")
+    missing = [k for k in SAC_KEYS + LOG_STD_KEYS if k not in sd]
+    if missing:
+        what = ("an actor-critic (PPO / A2C) checkpoint, no SAC actor" if all(k in sd for k in AC_KEYS)
+                else "no SB3 SAC MlpPolicy checkpoint")
+        raise ValueError(f"{zip_path}: {what}: missing {missing[:4]}")
+    a = [sd[k].float().numpy() for k in SAC_KEYS]
+    lw, lb = [sd[k].float().numpy() for k in LOG_STD_KEYS]
+    return make_squashed_actor(a[:4] + [np.concatenate([a[4], lw]), np.concatenate([a[5], lb])], RELU, "sac")
+
+
+def random_squashed_actor(h1: int, h2: int, seed: int = 0, activation: int = RELU) -> SquashedActor:
+    """Random-init squashed actor 38 -> h1 -> h2 -> mu [2] + log_std [2] (PyTorch nn.Linear default init)."""
+    rng = np.random.default_rng(seed)
+    arrs = []
+    for shp, fan_in in (((h1, 38), 38), ((h1,), 38), ((h2, h1), h1), ((h2,), h1), ((4, h2), h2), ((4,), h2)):
+        bound = 1.0 / np.sqrt(fan_in)
+        arrs.append(rng.uniform(-bound, bound, shp).astype(np.float32))
+    return make_squashed_actor(arrs, activation, "random")
+
+
+def squashed_actor_numpy(actor: SquashedActor, obs, eps, dtype=np.float64):
+    """Host restatement of the sampled SAC actor in `dtype` arithmetic on obs [n, 38] and standard normal pairs eps
+    [n, 2]: (u, s) -- u = unscale_action(tanh(mu + exp(clip(log_std, -20, 2)) * eps)) steps the env, s = scale_action(u)
+    is what the replay buffer keeps."""
+    dt = np.dtype(dtype).type
+    f = (lambda v: np.maximum(v, dt(0))) if actor.activation == RELU else np.tanh
+    x = np.asarray(obs, dtype=dt).reshape(-1, 38)
+    w1, b1, w2, b2, w3, b3 = [a.astype(dt) for a in actor.arrays]
+    h = f(x @ w1.T + b1)
+    h = f(h @ w2.T + b2)
+    out = h @ w3.T + b3
+    mu, ls = out[:, :2], np.clip(out[:, 2:], dt(LOG_STD_MIN), dt(LOG_STD_MAX))
+    t = np.tanh(mu + np.exp(ls) * np.asarray(eps, dt))
+    u = dt(-1) + (dt(0.5) * (t + dt(1))) * dt(2)
+    return u, dt(2) * ((u + dt(1)) / dt(2)) - dt(1)
