@@ -555,7 +555,8 @@ def run_scenario(ref, name, track, C, steps, policy, reset_on_lap=False, reset_a
 
 
 def track_tables(ref, track):
-    """Reference Track + wall builder tables (TrackLoader + CarPhysics._create_track_walls)."""
+    """Reference Track + wall builder tables (TrackLoader + CarPhysics._create_track_walls); `track`: a file name
+    under the reference's tracks/ or an absolute path."""
     track_path = os.path.join(ref, "tracks", track)
     hb = oracle_lib.OracleEnv(track_path, 1, 1)
     install_stubs(hb)
@@ -576,6 +577,43 @@ def track_tables(ref, track):
     sys.path.remove(ref)
     return dict(segments=segs, total_length=np.array(t.total_length), walls=walls, keys=keys,
                 has_banking=np.array(cp._track_has_banking()))
+
+
+def reference_start_position(ref, track_path):
+    """CarEnv.start_position after the reference's own _load_track (src/car_env.py:235-241)"""
+    import contextlib
+    hb = oracle_lib.OracleEnv(track_path, 1, 1)
+    install_stubs(hb)
+    purge_reference_modules()
+    sys.path.insert(0, ref)
+    with contextlib.redirect_stdout(io.StringIO()):
+        from src.car_env import CarEnv
+        env = CarEnv(render_mode=None, track_file=track_path, num_cars=1)
+    sys.path.remove(ref)
+    return np.array(env.start_position, np.float64)
+
+
+def generated_tracks(ref, out):
+    """tests/track_gen.py's family through the reference's TrackLoader and wall builder: tracks_generated.npz (the
+    texts as data, the segment and wall tables, the total length, the start position).  Written with fixed member
+    dates, so that a rerun reproduces the file byte for byte; it may not be larger than tracks.npz."""
+    import tempfile
+    if ROOT not in sys.path:
+        sys.path.insert(1, ROOT)          # track_gen checks its wall counts with the package's build_walls
+    import track_gen
+    allt = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for name in track_gen.FAMILY:
+            path = track_gen.write(tmp, name)
+            d = track_tables(ref, path)
+            allt[f"{name}__text"] = np.array(track_gen.text(name))
+            for k in ("segments", "walls", "total_length"):
+                allt[f"{name}__{k}"] = d[k]
+            allt[f"{name}__start_position"] = reference_start_position(ref, path)
+    path = os.path.join(out, "tracks_generated.npz")
+    savez_fixed(path, **allt)
+    assert os.path.getsize(path) <= os.path.getsize(os.path.join(out, "tracks.npz")), os.path.getsize(path)
+    print("tracks_generated.npz", len(track_gen.FAMILY), os.path.getsize(path), "bytes")
 
 
 SCENARIOS = [
@@ -627,6 +665,8 @@ def main():
                 allt[f"{tr[:-6]}__{k}"] = v
         np.savez_compressed(os.path.join(args.out, "tracks.npz"), **allt)
         print("tracks.npz", len(tracks))
+    if args.only in (None, "generated"):
+        generated_tracks(args.ref, args.out)
     for name, track, C, steps, pol, rol, rat, *extra in SCENARIOS:
         if args.only not in (None, name) and not (args.only == "new" and extra is not None and name in NEW):
             continue
@@ -651,6 +691,18 @@ def savez_lzma(path, **arrays):
             buf = io.BytesIO()
             np.save(buf, np.asanyarray(v))
             z.writestr(k + ".npy", buf.getvalue())
+
+
+def savez_fixed(path, **arrays):
+    """an .npz with LZMA members in the given order and a fixed member date: the same arrays give the same bytes"""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_LZMA) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.save(buf, np.asanyarray(v))
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_LZMA
+            zi.external_attr = 0o644 << 16
+            z.writestr(zi, buf.getvalue())
 
 
 if __name__ == "__main__":

@@ -111,7 +111,7 @@ static int load_track(otrack *t, const char *path, char *err, size_t errlen) {
         char *tok[8]; int nt = 0;
         for (char *p = strtok(line, " \t\r\n\v\f"); p && nt < 8; p = strtok(NULL, " \t\r\n\v\f")) tok[nt++] = p;
         if (nt == 0) continue;
-        if (t->nseg >= 63) { fclose(f); snprintf(err, errlen, "too many segments"); return -1; }
+        if (t->nseg >= 64) {   /* seg[] holds 64, the device's MAX_SEG */ fclose(f); snprintf(err, errlen, "too many segments"); return -1; }
         if (!strcmp(tok[0], "WIDTH")) {
             if (nt != 2) { fclose(f); snprintf(err, errlen, "WIDTH command requires exactly one argument"); return -1; }
             t->width = strtod(tok[1], NULL);

@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+import track_gen
 from golden_replay import GOLDEN, TRACKS
 from nascargymnasium_amd.track import build_walls, load_track
 
@@ -21,6 +22,22 @@ def test_python_track_pipeline_bit_exact(name):
     assert np.array_equal(t.segment_table(), g[f"{name}__segments"])
     assert t.total_length == float(g[f"{name}__total_length"])
     assert np.array_equal(build_walls(t), g[f"{name}__walls"])
+
+
+@pytest.mark.parametrize("name", track_gen.FAMILY)
+def test_generated_track_pipeline_bit_exact(name, tmp_path):
+    """tests/track_gen.py reproduces the texts stored in tracks_generated.npz, and track.py's tables of them equal the
+    reference's own (up to 64 segments, zero-length chords, dropped walls, no start line) bit for bit"""
+    g = np.load(os.path.join(GOLDEN, "tracks_generated.npz"))
+    assert track_gen.text(name) == str(g[f"{name}__text"])
+    t = load_track(track_gen.write(tmp_path, name))
+    assert len(t.segments) == track_gen.SEGMENTS[name]
+    assert np.array_equal(t.segment_table(), g[f"{name}__segments"])
+    assert t.total_length == float(g[f"{name}__total_length"])
+    walls = build_walls(t)
+    assert walls.shape == g[f"{name}__walls"].shape and len(walls) <= track_gen.MAX_WALLS
+    assert np.array_equal(walls, g[f"{name}__walls"])
+    assert np.array_equal(np.array(t.start_position, np.float64), g[f"{name}__start_position"])
 
 
 def test_loader_errors(tmp_path):

@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+import track_gen
 from golden_replay import GOLDEN, TRACKS, continuous_actions, first_mismatch, load, scenarios, start_kwargs
 from oracle_lib import OracleEnv
 
@@ -40,6 +41,31 @@ def test_track_tables_bit_exact(name, track_golden):
     _, inv = np.unique(keys, return_inverse=True)
     # same listener key string <=> same key id
     assert np.array_equal(inv[:, None] == inv[None, :], kid[:, None] == kid[None, :])
+
+
+@pytest.mark.parametrize("name", track_gen.FAMILY)
+def test_generated_track_tables_bit_exact(name, tmp_path):
+    """or_segments / or_walls of tests/track_gen.py's family against the reference's own tables"""
+    g = np.load(os.path.join(GOLDEN, "tracks_generated.npz"))
+    env = OracleEnv(track_gen.write(tmp_path, name))
+    d, _ = env.walls()
+    ref_walls = g[f"{name}__walls"]
+    assert d.shape[0] == ref_walls.shape[0]
+    assert np.array_equal(d, ref_walls[:, :4]) and np.all(ref_walls[:, 4] == 0.5)
+    assert np.array_equal(env.segments(), g[f"{name}__segments"])
+    assert env.total_length() == float(g[f"{name}__total_length"])
+    obs = env.reset()[0]      # the start position: obs[0:2] = (x, y) / 10000 of the car right after the reset
+    sp = g[f"{name}__start_position"]
+    assert np.array_equal(obs[0, 0, :2], (np.float32(sp).astype(np.float64) / 10000.0).astype(np.float32))
+    env.close()
+
+
+def test_oracle_takes_64_segments_and_no_more(tmp_path):
+    env = OracleEnv(track_gen.write(tmp_path, "s64", track_gen.too_many_segments(64)))
+    assert len(env.segments()) == 64 and env.total_length() == 100.0 + 63 * 10.0
+    env.close()
+    with pytest.raises(FileNotFoundError):       # or_create returns no handle
+        OracleEnv(track_gen.write(tmp_path, "seg65", track_gen.too_many_segments()))
 
 
 INFO_MAP = [  # golden info column -> oracle field

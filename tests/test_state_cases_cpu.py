@@ -208,6 +208,122 @@ def test_bank_and_input_sides():
     assert (rew[c.want["disabled"]] == 0.0).all() and (rew[~c.want["disabled"]] != 0.0).all()
 
 
+# ---------------------------------------------------------------- the track lookups on the generated tracks
+LOOKUP_SETS = [(n, C) for n, C in S.SETS
+               if S.CLASSES[n][0] in (S._chord_ties, S._startline_band, S._no_startline, S._on_track_query)]
+
+
+def _ends_where_probed(c, A):
+    """the builder's probe saw the position this step ends at"""
+    assert _same(A["f32"][f32i["xpx"]].astype(np.float64), c.meta["px"])
+    assert _same(A["f32"][f32i["xpy"]].astype(np.float64), c.meta["py"])
+
+
+@pytest.mark.parametrize("name,C", [s for s in LOOKUP_SETS if s[0].startswith("chord_ties")])
+def test_chord_ties_reach(name, C):
+    """What the chord_ties sets reach, counted on the oracle's positions after the step (of 2400 cars each; seg64 /
+    seg17 / ring4 / degenerate): nearest chord at index >= 16: 1722 / 155 / - / -; chord 16 nearest on seg17: 155;
+    a second chord within 2 screen_eps: 1598 / 1573 / 1909 / 1582; the two smallest distances equal or 1 ulp apart:
+    725 / 867 / 1017 / 877; runner-up with another banking: 2400 / 2317 / 2400 / 1937; projection clamped at 0: 9 /
+    25 / 218 / 79, at 1: 722 / 858 / 920 / 818; the two searches disagree on the chord: 0 / 5 / 35 / 80.  The
+    oracle's step leaves the banking of the chord `want` names, and the progress along it."""
+    c, A0, A, *_ = _after(name, C)
+    _ends_where_probed(c, A)
+    seg = S.track_tables(c.track)[0]
+    st = S.lookup_stats(seg, c.meta["px"], c.meta["py"])
+    assert np.array_equal(st["pbi"], c.want["pbi"]) and np.array_equal(st["bbi"], c.want["bbi"])
+    print(name, C, {k: (int((v >= 16).sum()) if k in ("pbi", "bbi") else [int((v == s).sum()) for s in (-1, 1)] if k == "clamp"
+                        else int(v.sum())) for k, v in st.items()}, "chord 16:", int((st["pbi"] == 16).sum()),
+          "searches disagree:", int((st["pbi"] != st["bbi"]).sum()))
+    if c.track == "seg64":
+        assert (st["pbi"] >= 16).sum() >= c.N // 4 and (st["bbi"] >= 16).sum() >= c.N // 4
+        assert len(np.unique(st["pbi"])) == 64
+    if c.track == "seg17":
+        assert (st["pbi"] == 16).sum() >= 50 and (st["bbi"] == 16).sum() >= 50
+    assert st["close"].sum() >= 200 and st["tie"].sum() >= 100 and st["bank_differs"].sum() >= 100
+    assert (st["clamp"] == -1).any() and (st["clamp"] == 1).any()
+    far = np.abs(c.meta["px"]) + np.abs(c.meta["py"])
+    assert (far > 5e4).sum() >= 20 and ((far > 1e3) & (far < 1e4)).sum() >= 20
+    # the oracle's own searches found these chords
+    assert _same(A["f64"][f64i["bank"]], seg[c.want["bbi"], 12])
+    k = c.want["pbi"]
+    sx, sy, dx, dy = seg[k, 2], seg[k, 3], seg[k, 4] - seg[k, 2], seg[k, 5] - seg[k, 3]
+    ll = dx * dx + dy * dy
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tt = S._clamp01(((c.meta["px"] - sx) * dx + (c.meta["py"] - sy) * dy) / ll)
+    qx, qy = np.where(ll < 1e-6, sx, sx + tt * dx), np.where(ll < 1e-6, sy, sy + tt * dy)
+    prefix = np.concatenate([[0.0], np.cumsum(np.sqrt(S.P2(seg[:, 4] - seg[:, 2]) + S.P2(seg[:, 5] - seg[:, 3])))])[k]
+    assert _same(A["f64"][f64i["prog_hist"]], prefix + np.sqrt(S.P2(qx - sx) + S.P2(qy - sy)))
+
+
+@pytest.mark.parametrize("name,C", [s for s in LOOKUP_SETS if s[0].startswith("startline_band")])
+def test_startline_band_outcomes(name, C):
+    """every offset of band_offsets() (0, +-1e-6, +-screen_eps / 2, +-screen_eps, +-2 screen_eps, +-1 m from the
+    capsule's edge) is met to BAND_TOL on both sides and around both ends (measured: to 5.3e-8 on seg64, whose start
+    line is rotated and 350 m out, and to 4.6e-8 on degenerate); (now, before) takes all four values; of 2400 cars,
+    206 / 233 (seg64 / degenerate) complete a lap and 216 / 244 cross for the first time; the cars end where they
+    were put"""
+    c, A0, A, *_ = _after(name, C)
+    _ends_where_probed(c, A)
+    assert _same(A["f32"][f32i["xpx"]], A0["f32"][f32i["xpx"]]) and _same(A["f32"][f32i["xpy"]], A0["f32"][f32i["xpy"]])
+    m, w = c.meta, c.want
+    err = np.abs(m["edge"] - m["off"])
+    worst = 0.0
+    for p in range(S.BAND_PLACES):
+        for j in range(len(S.band_offsets(1.0))):
+            sel = (m["place"] == p) & (m["joff"] == j)
+            assert sel.sum() >= 5 and err[sel].min() <= S.BAND_TOL, (p, j, err[sel].min())
+            worst = max(worst, err[sel].min())
+            nominal = S.band_offsets(1.0)[j]
+            if nominal != 0.0:          # and on the side of the edge it was aimed at
+                assert (np.sign(m["edge"][sel][err[sel] <= S.BAND_TOL]) == np.sign(nominal)).all()
+    if c.track == "degenerate":       # its start line runs along +x at the origin: float32 holds the edge itself
+        assert (m["edge"] == 0.0).any()
+    for now in (False, True):
+        for before in (False, True):
+            assert ((w["now"] == now) & (w["before"] == before)).sum() >= 100
+    laps = A["i32"][i32i["lt_laps"]] - A0["i32"][i32i["lt_laps"]]
+    assert np.array_equal(laps == 1, w["lap"]) and ((laps == 0) | (laps == 1)).all() and w["lap"].any()
+    first = (A["i32"][i32i["lt_crossed"]] == 1) & (A0["i32"][i32i["lt_crossed"]] == 0)
+    assert np.array_equal(first, w["first"]) and w["first"].any()
+    assert np.array_equal(A["i32"][i32i["lt_has_pos"]], np.where(w["now"], 3, 1))
+    print(name, C, "worst best offset error", worst, "laps", int(w["lap"].sum()), "first crossings", int(w["first"].sum()))
+
+
+def test_no_startline_outcomes():
+    """without a STARTLINE no lap field changes but the position, and lt_dist takes the move of the cars that had one"""
+    (name, C), = [s for s in LOOKUP_SETS if s[0] == "no_startline"]
+    c, A0, A, *_ = _after(name, C)
+    for f in ("lt_timing", "lt_has_last", "lt_has_best", "lt_crossed", "lt_laps"):
+        assert np.array_equal(A["i32"][i32i[f]], A0["i32"][i32i[f]]), f
+    for f in ("lt_start", "lt_last", "lt_best"):
+        assert _same(A["f64"][f64i[f]], A0["f64"][f64i[f]]), f
+    assert (A["i32"][i32i["lt_has_pos"]] == 1).all()
+    dx = A["f32"][f32i["xpx"]].astype(np.float64) - A0["f64"][f64i["lt_px"]]
+    dy = A["f32"][f32i["xpy"]].astype(np.float64) - A0["f64"][f64i["lt_py"]]
+    d = np.sqrt(dx * dx + dy * dy)
+    assert (d[c.want["has"]] > 0.3).any() and (d < 50.0).all()
+    assert _same(A["f64"][f64i["lt_dist"]], np.where(c.want["has"], A0["f64"][f64i["lt_dist"]] + d, A0["f64"][f64i["lt_dist"]]))
+    tm = c.want["timing"]
+    assert (A["f64"][f64i["lt_cur"]][tm] > 29.9).all() and _same(A["f64"][f64i["lt_cur"]][~tm], A0["f64"][f64i["lt_cur"]][~tm])
+
+
+@pytest.mark.parametrize("name,C", [s for s in LOOKUP_SETS if s[0].startswith("on_track_query")])
+def test_on_track_query_outcomes(name, C):
+    """on a wall / off every wall, of 2400 cars: 1460 / 940 on seg64, 1568 / 832 on degenerate; decided by the vertex
+    distance (inside no box, within 0.5 m of a corner): 321 / 459.  The float64 geometry of wall_query agrees with the
+    oracle's float32 query for every car it decides by more than 0.1 mm (114 / 93 cars lie closer)."""
+    c, A0, A, *_ = _after(name, C)
+    _ends_where_probed(c, A)
+    w = c.want
+    on = S.oracle_info(name, C)[:, 0] == 0.0
+    sure = c.meta["margin"] > 1e-4
+    assert sure.sum() > 0.9 * c.N and np.array_equal(on[sure], w["on_wall"][sure])
+    assert on.sum() >= c.N // 5 and (~on).sum() >= c.N // 5
+    assert (w["vertex"] & sure & on).sum() >= 50
+    print(name, C, "on a wall", int(on.sum()), "by the vertex distance", int((w["vertex"] & sure).sum()), "unsure", int((~sure).sum()))
+
+
 # ---------------------------------------------------------------- the read-back
 @pytest.mark.parametrize("name,C", [("impact_crowded", 10), ("lap_gate", 1), ("termination_reset_on_lap", 3)])
 def test_set_get_car_full_is_identity(name, C):
