@@ -264,7 +264,9 @@ int nascar_get_car_visibility(NascarHandle* h);
  * perf_first_fast; 0 frees it (the info fields then read -1 / 0 / -1).  Off by default. */
 int nascar_set_perf_history(NascarHandle* h, int32_t enable, void* stream);
 
-/* Raw state snapshot / restore (checkpointing and state-injection parity tests). */
+/* Raw state snapshot / restore (checkpointing and state-injection parity tests).  The snapshot does not carry the
+ * random-track map (nascar_set_random_tracks) nor the running normalisation's statistics and returns
+ * (nascar_get_norm_stats / nascar_set_norm_stats carry those). */
 int64_t nascar_state_bytes(NascarHandle* h);
 int nascar_get_state(NascarHandle* h, void* dst_device, void* stream);
 int nascar_set_state(NascarHandle* h, const void* src_device, void* stream);
@@ -403,6 +405,68 @@ int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps,
                    void* stream);
 int nascar_gae(NascarHandle* h, const float* reward, const float* values, const float* timeout_values,
                const uint8_t* env_flags, int32_t steps, double gamma, double lambda, float* adv, float* ret, void* stream);
+
+/* Running normalisation: Stable-Baselines3's VecNormalize (common/vec_env/vec_normalize.py, common/running_mean_std.py
+ * of SB3 2.7.0), which the reference wraps its A2C training envs in (learn/a2c.py:94-100: norm_obs, norm_reward,
+ * clip_obs = 1.0, gamma = 0.99) and which usually accompanies SB3's PPO, on the device.  Every car slot is one of SB3's
+ * envs: a batch is the N = E * C rows of a step, disabled cars' rows included, and an env's done flag applies to the
+ * returns of all its cars.
+ * Statistics (float64, on the device, outside the state arena: nascar_get_state / nascar_set_state do not carry them, as
+ * they do not carry the random-track map): obs_mean [38], obs_var [38], obs_count, ret_mean, ret_var, ret_count -- 80
+ * doubles in this order, the `stats` record below -- and returns [N].  Fresh: mean 0, var 1, count 1e-4, returns 0.
+ * RunningMeanStd.update(batch), every expression left to right in float64:
+ *     bm, bv = batch mean and population variance per column, bc = N
+ *     delta = bm - mean;  tot = count + bc;  new_mean = mean + delta * bc / tot
+ *     m2 = var * count + bv * bc + delta^2 * count * bc / (count + bc);  new_var = m2 / (count + bc);  new_count = bc + count
+ *   ONE DEVIATION: the batch moments are taken in float64 over the float32 rows (SB3 lets NumPy accumulate them in
+ *   float32; this is the quantity that approximates).  Each workgroup of 256 rows (a rule of N alone) takes its mean and
+ *   its sum of squares about that mean; the workgroups' (count, mean, M2) are merged in workgroup order.  No atomics:
+ *   the statistics are the same bits from run to run and whatever the rollout streams.
+ * normalize_obs(x) = (float)clip(((double)x - mean) / sqrt(var + epsilon), -clip_obs, clip_obs), normalize_reward(r) =
+ *   (float)clip((double)r / sqrt(ret_var + epsilon), -clip_reward, clip_reward): a float64 subtract, divide, clip, one cast.
+ * nascar_set_normalize: cfg NULL switches normalisation off (the statistics are kept until it is switched on again,
+ *   which starts from fresh ones); otherwise the settings, which may change while it is on (training = 0 freezes the
+ *   statistics).  clip_obs, clip_reward and epsilon must be finite and positive, gamma finite and >= 0.  Synchronises
+ *   `stream` when it switches on.  nascar_get_normalize returns 1 / 0 for on / off and the settings.
+ * nascar_get_norm_stats: the statistics into device buffers stats [80] and returns [N] (either may be NULL).
+ * nascar_set_norm_stats: host arrays stats [80] and returns [N] (NULL: kept); every entry finite, no negative variance,
+ *   both counts positive.  Synchronises `stream`.
+ * nascar_normalize_reset: VecNormalize.reset on the observation a full nascar_reset wrote: returns = 0, the obs update
+ *   when training, obs_out = normalize_obs(obs_raw).
+ * nascar_normalize_step: VecNormalize.step_wait on one step's outputs, in SB3's order: the obs update (training and
+ *   norm_obs), obs_out = normalize_obs(obs_raw), returns = returns * gamma + reward and the returns update (training and
+ *   norm_reward), reward_out = normalize_reward(reward_raw), term_out = normalize_obs(term_obs) for the cars of done envs
+ *   (terminated | truncated in env_flags) under the statistics as they now stand -- other rows of term_out are left as
+ *   they are, term_obs / term_out NULL: none, and they may be one buffer -- and returns = 0 for the cars of done envs
+ *   last.  obs_raw holds the reset observation of auto-reset envs: SB3 includes it in the update, and so does this.
+ *   A flag that is off copies its input.  obs_raw 8-byte aligned; all buffers device pointers, [N][38] / [N] / [E].
+ * nascar_collect_normalized: nascar_collect under normalisation.  obs_raw [N][38] is the engine's raw observation, in /
+ *   out (the step and random-track mode read and write it; it stays raw); obs record 0 holds the NORMALISED current
+ *   observation on entry (what nascar_normalize_reset / _step wrote) and record k + 1 the normalised one after step k;
+ *   the actor samples on and the critic values record k; reward [steps][N] takes the normalised rewards and raw_reward
+ *   [steps][N] the raw ones; timeout_values are V of the normalised terminal observation under the statistics after step
+ *   k's update.  Identical, bit for bit and in the final statistics, to `steps` x (nascar_policy_actions(6) on the
+ *   normalised observation + nascar_step(auto_reset, terminal_obs) + nascar_normalize_step).  While the statistics are
+ *   updated (training with either flag) step k + 1 needs every env's step-k observation: the call runs as one shard;
+ *   with frozen statistics the work is row-local and the shards run on unsynchronised.  Either way the results do not
+ *   depend on the rollout streams.  Refusals as nascar_collect's (rollout streams 0 and the pipelined rollout among them).
+ * While normalisation is on, nascar_collect (use nascar_collect_normalized) and nascar_collect_transitions (off-policy
+ *   normalisation happens at sample time and is not provided) fail. */
+typedef struct NascarNormalize {
+    int32_t norm_obs, norm_reward, training;
+    int32_t pad_;
+    double clip_obs, clip_reward, gamma, epsilon;
+} NascarNormalize;
+int nascar_set_normalize(NascarHandle* h, const NascarNormalize* cfg, void* stream);
+int nascar_get_normalize(NascarHandle* h, NascarNormalize* cfg);
+int nascar_get_norm_stats(NascarHandle* h, double* stats, double* returns, void* stream);
+int nascar_set_norm_stats(NascarHandle* h, const double* stats, const double* returns, void* stream);
+int nascar_normalize_reset(NascarHandle* h, const float* obs_raw, float* obs_out, void* stream);
+int nascar_normalize_step(NascarHandle* h, const float* obs_raw, const float* reward_raw, const uint8_t* env_flags,
+                          const float* term_obs, float* obs_out, float* reward_out, float* term_out, void* stream);
+int nascar_collect_normalized(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps, float* obs_raw, float* obs,
+                              float* reward, float* raw_reward, uint8_t* car_flags, uint8_t* env_flags, float* actions,
+                              float* logp, float* values, float* timeout_values, void* stream);
 
 /* Off-policy collection: the loop of SB3's off-policy algorithms, as learn/sac.py, learn/td3.py, learn/td3_n.py and
  * learn/ddpg.py run it (OffPolicyAlgorithm.collect_rollouts, off_policy_algorithm.py: _sample_action, env.step,

@@ -9,7 +9,8 @@ one fused HIP kernel for gfx950 over E envs x C cars (libnascar.so, include/nasc
 from .track import Track, available_tracks, build_walls, load_track, track_path  # noqa: F401
 
 __all__ = ["Track", "available_tracks", "build_walls", "load_track", "track_path", "BatchedCarEnv", "CarEnv",
-           "BaseEnv", "VecCarEnv", "RolloutBatch", "ActorCriticNet", "ReplayBuffer", "ReplaySamples", "SquashedActorNet"]
+           "BaseEnv", "VecCarEnv", "RolloutBatch", "ActorCriticNet", "ReplayBuffer", "ReplaySamples", "SquashedActorNet",
+           "NormalizedRolloutBatch", "NormStats"]
 
 
 def __getattr__(name):   # torch-dependent pieces load lazily
@@ -22,7 +23,10 @@ def __getattr__(name):   # torch-dependent pieces load lazily
     if name == "VecCarEnv":
         from .vec_env import VecCarEnv
         return VecCarEnv
-    if name in ("RolloutBatch", "ActorCriticNet"):
+    if name == "NormStats":
+        from .normalize import NormStats
+        return NormStats
+    if name in ("RolloutBatch", "ActorCriticNet", "NormalizedRolloutBatch"):
         from . import onpolicy
         return getattr(onpolicy, name)
     if name in ("ReplayBuffer", "ReplaySamples", "SquashedActorNet"):

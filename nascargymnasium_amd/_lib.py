@@ -54,6 +54,16 @@ class NascarReplay(ctypes.Structure):
                [("capacity", ctypes.c_int32)]
 
 
+class NascarNormalize(ctypes.Structure):
+    """include/nascar.h NascarNormalize: the settings of the running normalisation (SB3's VecNormalize)."""
+    _fields_ = [("norm_obs", ctypes.c_int32), ("norm_reward", ctypes.c_int32), ("training", ctypes.c_int32),
+                ("pad_", ctypes.c_int32), ("clip_obs", ctypes.c_double), ("clip_reward", ctypes.c_double),
+                ("gamma", ctypes.c_double), ("epsilon", ctypes.c_double)]
+
+
+NORM_STATS = 80     # nascar_get_norm_stats record: obs_mean [38], obs_var [38], obs_count, ret_mean, ret_var, ret_count
+
+
 class NascarConfig(ctypes.Structure):
     _fields_ = [("num_envs", ctypes.c_int32), ("num_cars", ctypes.c_int32), ("reset_on_lap", ctypes.c_int32),
                 ("device", ctypes.c_int32), ("start_x", ctypes.c_double), ("start_y", ctypes.c_double),
@@ -165,6 +175,20 @@ def lib():
     L.nascar_collect.restype = ctypes.c_int
     L.nascar_gae.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_double, ctypes.c_double, vp, vp, vp]
     L.nascar_gae.restype = ctypes.c_int
+    L.nascar_set_normalize.argtypes = [vp, ctypes.POINTER(NascarNormalize), vp]
+    L.nascar_set_normalize.restype = ctypes.c_int
+    L.nascar_get_normalize.argtypes = [vp, ctypes.POINTER(NascarNormalize)]
+    L.nascar_get_normalize.restype = ctypes.c_int
+    L.nascar_get_norm_stats.argtypes = [vp, vp, vp, vp]
+    L.nascar_get_norm_stats.restype = ctypes.c_int
+    L.nascar_set_norm_stats.argtypes = [vp, d_p, d_p, vp]
+    L.nascar_set_norm_stats.restype = ctypes.c_int
+    L.nascar_normalize_reset.argtypes = [vp, vp, vp, vp]
+    L.nascar_normalize_reset.restype = ctypes.c_int
+    L.nascar_normalize_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.nascar_normalize_step.restype = ctypes.c_int
+    L.nascar_collect_normalized.argtypes = [vp, u64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.nascar_collect_normalized.restype = ctypes.c_int
     L.nascar_set_explorer.argtypes = [vp, i32, fp]
     L.nascar_set_explorer.restype = ctypes.c_int
     L.nascar_collect_transitions.argtypes = [vp, i32, u64, i64, i32, vp, ctypes.POINTER(NascarReplay), i32, vp]
@@ -222,6 +246,8 @@ EXPORTED = ["nascar_create", "nascar_destroy", "nascar_last_error", "nascar_add_
             "nascar_set_genomes", "nascar_set_fitness", "nascar_get_fitness",
             "nascar_update_controller", "nascar_set_actor_critic", "nascar_collect", "nascar_gae",
             "nascar_set_explorer", "nascar_collect_transitions", "nascar_replay_sample",
+            "nascar_set_normalize", "nascar_get_normalize", "nascar_get_norm_stats", "nascar_set_norm_stats",
+            "nascar_normalize_reset", "nascar_normalize_step", "nascar_collect_normalized",
             "nascar_debug_sincosf", "nascar_debug_f64math", "nascar_debug_toi", "nascar_debug_collide", "nascar_debug_car_contact", "nascar_debug_sensors", "nascar_track_draw", "nascar_set_random_tracks",
             "nascar_get_env_tracks", "nascar_vec_post", "nascar_check_actions", "nascar_set_track_cache",
             "nascar_prebuild_track", "nascar_debug_block_map"]

@@ -76,6 +76,8 @@ class BatchedCarEnv:
         self.terminal_obs = torch.zeros_like(self.obs)
         self._info = torch.zeros(self.E, self.C, _lib.N_INFO, dtype=torch.float64, device=dev)
         self._actions = torch.zeros(self.E, self.C, 2, dtype=torch.float32, device=dev)
+        self.normalize = None       # set_normalize: the settings while normalisation is on
+        self._norm_obs = self._norm_reward = self._norm_terminal_obs = None
         if perf_history:
             self.set_perf_history(True)
 
@@ -272,10 +274,15 @@ class BatchedCarEnv:
 
     # ------------------------------------------------------------------ core API
     def reset(self, env_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """CarEnv.reset for all envs (or those with env_mask[e] != 0, uint8[E] on device)."""
+        """CarEnv.reset for all envs (or those with env_mask[e] != 0, uint8[E] on device).  Under set_normalize a full
+        reset also performs VecNormalize.reset and returns the normalised observation (`norm_obs`); a masked reset does
+        not (SB3's in-step resets are ordinary steps)."""
         with torch.cuda.device(self.device):
             m = None if env_mask is None else env_mask.to(self.device, torch.uint8).contiguous()
             _lib.check(self.L.nascar_reset(self.h, _ptr(m), _ptr(self.obs), _stream()))
+            if m is None and self.normalize is not None:
+                _lib.check(self.L.nascar_normalize_reset(self.h, _ptr(self.obs), _ptr(self._norm_buffers()[0]), _stream()))
+                return self._norm_obs
         return self.obs
 
     def step(self, actions: torch.Tensor, auto_reset: bool = False, terminal_obs: bool = False):
@@ -537,32 +544,137 @@ class BatchedCarEnv:
         limit cut (truncated, not terminated) record V(terminal obs) for the reward bootstrap.  Runs on the sharded
         rollout's streams; equals `steps` x (policy_actions(6, seed, step0 + k) + step(auto_reset=True)).  Returns a
         nascargymnasium_amd.onpolicy.RolloutBatch; `out`: a RolloutBatch of caller-owned buffers with at least `steps`
-        records (steps + 1 of obs and values) to write into."""
-        from .onpolicy import RolloutBatch
+        records (steps + 1 of obs and values) to write into.
+        Under set_normalize the loop is the one SB3 runs around a VecNormalize: the actor-critic sees `norm_obs`, every
+        step ends with `normalize_step`, GAE takes the normalised rewards, and the batch is a NormalizedRolloutBatch
+        (obs and rewards normalised, raw_rewards beside them; `out` then is one too); equals `steps` x
+        (policy_actions(6, obs=norm_obs) + step(auto_reset=True, terminal_obs=True) + normalize_step(terminal_obs=True))."""
+        from .onpolicy import NormalizedRolloutBatch, RolloutBatch
         K = int(steps)
         if K < 1:
             raise ValueError("collect needs steps >= 1")
         E, C = self.E, self.C
-        spec = RolloutBatch.spec(E, C)
+        Batch = RolloutBatch if self.normalize is None else NormalizedRolloutBatch
+        spec = Batch.spec(E, C)
         if out is None:
-            out = RolloutBatch(*[torch.empty((K + extra, *inner), dtype=dt, device=self.device)
-                                 for _name, dt, inner, extra in spec])
+            out = Batch(*[torch.empty((K + extra, *inner), dtype=dt, device=self.device)
+                          for _name, dt, inner, extra in spec])
         else:
+            if len(out) != len(spec):
+                raise ValueError(f"out must be a {Batch.__name__} ({len(spec)} buffers), got {len(out)}")
             for (name, dt, inner, extra), t in zip(spec, out):
                 self._check_record_buffer(name, t, dt, inner, K + extra)
         with torch.cuda.device(self.device):
-            out.obs[0].copy_(self.obs)
-            _lib.check(self.L.nascar_collect(self.h, int(seed), int(step0), K, _ptr(out.obs), _ptr(out.rewards),
-                                             _ptr(out.car_flags), _ptr(out.env_flags), _ptr(out.actions),
-                                             _ptr(out.log_probs), _ptr(out.values), _ptr(out.timeout_values), _stream()))
+            if self.normalize is None:
+                out.obs[0].copy_(self.obs)
+                _lib.check(self.L.nascar_collect(self.h, int(seed), int(step0), K, _ptr(out.obs), _ptr(out.rewards),
+                                                 _ptr(out.car_flags), _ptr(out.env_flags), _ptr(out.actions),
+                                                 _ptr(out.log_probs), _ptr(out.values), _ptr(out.timeout_values), _stream()))
+            else:
+                nobs, nrew, _nterm = self._norm_buffers()
+                out.obs[0].copy_(nobs)
+                _lib.check(self.L.nascar_collect_normalized(
+                    self.h, int(seed), int(step0), K, _ptr(self.obs), _ptr(out.obs), _ptr(out.rewards), _ptr(out.raw_rewards),
+                    _ptr(out.car_flags), _ptr(out.env_flags), _ptr(out.actions), _ptr(out.log_probs), _ptr(out.values),
+                    _ptr(out.timeout_values), _stream()))
             _lib.check(self.L.nascar_gae(self.h, _ptr(out.rewards), _ptr(out.values), _ptr(out.timeout_values),
                                          _ptr(out.env_flags), K, float(gamma), float(gae_lambda), _ptr(out.advantages),
                                          _ptr(out.returns), _stream()))
-            self.reward.copy_(out.rewards[K - 1]); self.car_flags.copy_(out.car_flags[K - 1])
-            self.env_flags.copy_(out.env_flags[K - 1]); self.obs.copy_(out.obs[K])
+            self.car_flags.copy_(out.car_flags[K - 1]); self.env_flags.copy_(out.env_flags[K - 1])
+            if self.normalize is None:
+                self.reward.copy_(out.rewards[K - 1]); self.obs.copy_(out.obs[K])
+            else:                                   # (self.obs, raw, was stepped in place)
+                self.reward.copy_(out.raw_rewards[K - 1]); nrew.copy_(out.rewards[K - 1]); nobs.copy_(out.obs[K])
         if any(t.shape[0] != K + extra for (_n, _d, _i, extra), t in zip(spec, out)):   # larger caller buffers: this call's records
-            out = RolloutBatch(*[t[:K + extra] for (_n, _d, _i, extra), t in zip(spec, out)])
+            out = Batch(*[t[:K + extra] for (_n, _d, _i, extra), t in zip(spec, out)])
         return out
+
+    # ------------------------------------------------------------------ running normalisation (SB3's VecNormalize)
+    def set_normalize(self, norm_obs: bool = True, norm_reward: Optional[bool] = None, clip_obs: float = 10.0, clip_reward: float = 10.0,
+                      gamma: float = 0.99, epsilon: float = 1e-8, training: bool = True, stats=None):
+        """SB3's VecNormalize on the device (the reference trains A2C under VecNormalize(norm_obs=True, norm_reward=True,
+        clip_obs=1.0, gamma=0.99), learn/a2c.py:94-100): running float64 mean / variance of the 38 observation columns
+        and of the discounted returns over the N = E * C car slots (each is one of SB3's envs), updated from every
+        step's batch while `training`, frozen otherwise.  `collect` then runs its loop under it, `normalize_step` /
+        `norm_obs` serve a per-step loop, and a full `reset()` performs VecNormalize.reset.  The batch moments are taken
+        in float64 over the float32 rows (SB3's NumPy takes them in float32).  `stats`: a NormStats to start from
+        (default: fresh ones when normalisation was off, the current ones when only the settings change).
+        `set_normalize(False)` switches it off (rewards alone: `set_normalize(norm_obs=False, norm_reward=True)`; norm_reward
+        left out means True).  While it is on `collect_transitions` raises, and the state snapshot
+        (get_state / set_state) does not carry the statistics: norm_stats() / load_norm_stats() do."""
+        with torch.cuda.device(self.device):
+            if not norm_obs and not norm_reward:
+                _lib.check(self.L.nascar_set_normalize(self.h, None, _stream()))
+                self.normalize = None
+                return
+            norm_reward = True if norm_reward is None else norm_reward
+            cfg = _lib.NascarNormalize(int(bool(norm_obs)), int(bool(norm_reward)), int(bool(training)), 0, float(clip_obs),
+                                       float(clip_reward), float(gamma), float(epsilon))
+            _lib.check(self.L.nascar_set_normalize(self.h, ctypes.byref(cfg), _stream()))
+        self.normalize = dict(norm_obs=bool(norm_obs), norm_reward=bool(norm_reward), clip_obs=float(clip_obs),
+                              clip_reward=float(clip_reward), gamma=float(gamma), epsilon=float(epsilon),
+                              training=bool(training))
+        if stats is not None:
+            self.load_norm_stats(stats)
+
+    def _norm_buffers(self):
+        if self.normalize is None:
+            raise RuntimeError("normalisation is off (set_normalize)")
+        if self._norm_obs is None:
+            self._norm_obs = torch.zeros_like(self.obs)
+            self._norm_reward = torch.zeros_like(self.reward)
+            self._norm_terminal_obs = torch.zeros_like(self.obs)
+        return self._norm_obs, self._norm_reward, self._norm_terminal_obs
+
+    @property
+    def norm_obs(self) -> torch.Tensor:
+        """the normalised current observation [E, C, 38], as the last full reset(), normalize_step() or collect() left it"""
+        return self._norm_buffers()[0]
+
+    @property
+    def norm_reward(self) -> torch.Tensor:
+        """the normalised reward [E, C] of the last normalize_step() or collect()"""
+        return self._norm_buffers()[1]
+
+    @property
+    def norm_terminal_obs(self) -> torch.Tensor:
+        """normalize_step(terminal_obs=True): the normalised terminal observation of the cars of envs that ended (other
+        rows are stale)"""
+        return self._norm_buffers()[2]
+
+    def normalize_step(self, terminal_obs: bool = False):
+        """VecNormalize.step_wait on the outputs of the last step (`obs`, `reward`, `env_flags`, and `terminal_obs` when
+        asked: that step must have been taken with terminal_obs=True): updates the statistics while training, then
+        returns (norm_obs, norm_reward); `norm_terminal_obs` holds the normalised terminal rows of the envs that ended."""
+        nobs, nrew, nterm = self._norm_buffers()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.nascar_normalize_step(self.h, _ptr(self.obs), _ptr(self.reward), _ptr(self.env_flags),
+                                                    _ptr(self.terminal_obs) if terminal_obs else None, _ptr(nobs), _ptr(nrew),
+                                                    _ptr(nterm) if terminal_obs else None, _stream()))
+        return nobs, nrew
+
+    def norm_stats(self):
+        """the running statistics and returns as a nascargymnasium_amd.normalize.NormStats (one host synchronisation)"""
+        from .normalize import NormStats
+        buf = torch.empty(_lib.NORM_STATS + self.N, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.nascar_get_norm_stats(self.h, _ptr(buf), _ptr(buf[_lib.NORM_STATS:]), _stream()))
+        a = buf.cpu().numpy()
+        return NormStats.from_record(a[:_lib.NORM_STATS], returns=a[_lib.NORM_STATS:].copy())
+
+    def load_norm_stats(self, stats):
+        """Upload a NormStats (its `returns`, when it has them, must hold one entry per car slot)."""
+        stats.validate()
+        rec = np.ascontiguousarray(stats.record())
+        ret = None
+        if stats.returns is not None:
+            ret = np.ascontiguousarray(stats.returns, np.float64)
+            if ret.size != self.N:
+                raise ValueError(f"NormStats.returns holds {ret.size} entries, the env has {self.N} car slots")
+        dp = ctypes.POINTER(ctypes.c_double)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.nascar_set_norm_stats(self.h, rec.ctypes.data_as(dp),
+                                                    ret.ctypes.data_as(dp) if ret is not None else None, _stream()))
 
     def gae(self, rewards, values, timeout_values, env_flags, gamma: float = 0.99, gae_lambda: float = 0.95):
         """(advantages, returns) [K, E, C] of SB3's RolloutBuffer.compute_returns_and_advantage, float32 in its operation

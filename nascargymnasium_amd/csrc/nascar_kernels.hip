@@ -1498,6 +1498,7 @@ __global__ void field_policy_kernel(int n0, int n1, int C, FieldCodes F, uint64_
   act[2 * n] = a0; act[2 * n + 1] = a1;
 }
 
+#include "nascar_norm.h"     // running observation / return normalisation (nascar_set_normalize)
 #include "nascar_replay.h"   // the off-policy collection's ring kernels (they take policy 0's draw from policy_car)
 
 // Genome driver (policy 5, NASCAR_CTRL_GENOME): BaseController._fallback_control with its constants replaced by the
@@ -2963,6 +2964,10 @@ struct NascarHandle {
   // with the noise sigma), and the car / env flags [N] / [E] of the step a transition is assembled from (one allocation)
   int ex_id = -1; float ex_sigma[2] = {0.0f, 0.0f};
   uint8_t* d_rp_cf = nullptr; uint8_t* d_rp_ef = nullptr;
+  // running normalisation (nascar_set_normalize): the settings, and one allocation outside the state arena -- the
+  // statistics record [NORM_STATS], returns [N] and the moments kernel's partials [norm_groups][39][2], float64
+  bool norm_on = false; NascarNormalize norm{};
+  double* d_norm = nullptr; double* d_norm_ret = nullptr; double* d_norm_part = nullptr; int norm_groups = 0;
   // genome drivers (policy 5, NASCAR_CTRL_GENOME): the per-car gene records, outside the state arena; their upload is
   // staged in pinned memory and ordered on the caller's stream
   GenomeRec* d_genome = nullptr; bool genome_set = false;
@@ -3142,6 +3147,7 @@ extern "C" void nascar_destroy(NascarHandle* h) {
   hipFree(h->d_ctrl);
   hipFree(h->d_term);
   hipFree(h->d_rp_cf);   // (d_rp_ef is its tail)
+  hipFree(h->d_norm);    // (the returns and the partials are its tail)
   hipFree(h->d_rt);
   hipFree(h->d_genome);
   hipFree(h->d_fit);
@@ -3677,6 +3683,17 @@ static int launch_explorer(NascarHandle* h, int c0, int n, uint64_t seed, int64_
                            float* s_out, hipStream_t s);
 // the ring of nascar_collect_transitions (the sharded rollout fills slot (pos + k) % capacity at step k) and its source
 struct ReplayRun { NascarReplay R; int pos, source; };
+// nascar_collect_normalized: the engine's raw observation [N][38] (the step runs in place on it) and the raw reward
+// records [steps][N]; the rollout's own obs / reward records take the normalised values
+struct NormRun { float* obs_raw; float* raw_reward; };
+// One VecNormalize.step_wait for the cars [c0, c1) on stream s (defined with nascar_normalize_step); update: the
+// statistics first (whole batch: c0 = 0, c1 = N)
+static int norm_step_range(NascarHandle* h, size_t c0, size_t c1, bool update, const float* obs_raw, const float* reward_raw,
+                           const uint8_t* env_flags, const float* term, float* obs_out, float* reward_out, float* term_out,
+                           hipStream_t s);
+static bool norm_updates(const NascarHandle* h) {
+  return h->norm_on && h->norm.training && (h->norm.norm_obs || h->norm.norm_reward);
+}
 // Shard s of S: its workgroups [b0, b1) and its cars [c0, c1) -- contiguous because the block map is the identity or
 // there is one shard, which holds every car.  b0 < 0 (nascar_policy_actions): no workgroups, the cars alone.
 struct ShardRange { int b0, b1; size_t c0, c1; };
@@ -3756,8 +3773,12 @@ static int upload_params(NascarHandle* h, const Params& P, hipStream_t stream) {
 }
 static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed, int64_t step0, int32_t steps, float* obs,
                            float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, int32_t traj,
-                           hipStream_t stream, const CollectBufs* col = nullptr, const ReplayRun* rp = nullptr) {
+                           hipStream_t stream, const CollectBufs* col = nullptr, const ReplayRun* rp = nullptr,
+                           const NormRun* nr = nullptr) {
   S = std::max(1, std::min(S, h->nblocks));
+  // running statistics: step k + 1 is normalised with every env's step-k observation, so the batch steps as one shard
+  // (frozen statistics are row-local: the shards keep running unsynchronised)
+  if (nr && norm_updates(h)) S = 1;
   const bool rt = h->rt_on && auto_reset;
   if (h->rt_on) S = 1;   // random-track mode: the block map changes between steps, so no shard owns a fixed set of envs
   // the actions come from a launch of their own (launch_actions; the callers have checked policy_ready), into d_ro_act
@@ -3789,12 +3810,17 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
       const size_t ko = traj ? (size_t)k : 0;
       float* o_in = obs_traj ? obs + (size_t)k * NC * 38 : obs;
       float* o_out = obs_traj ? obs + (size_t)(k + 1) * NC * 38 : obs;
+      // normalised collection: the actor-critic reads record k, the step runs in place on the raw observation, and
+      // record k + 1 is written by the normalisation after the step
+      float* a_in = o_in;
+      float* n_out = o_out;
+      if (nr) o_in = o_out = nr->obs_raw;
       uint8_t* ef = rp ? h->d_rp_ef : step_env_flags(h, env_flags ? env_flags + ko * E : nullptr, auto_reset);
       // nascar_collect_transitions: the step runs in place on obs and writes its reward into the ring's slot; the
       // explorer writes the slot's scaled action beside the action that steps the envs
       const size_t slot = rp ? (size_t)((rp->pos + (int64_t)k) % rp->R.capacity) : 0;
       const size_t slot1 = rp ? (slot + 1) % (size_t)rp->R.capacity : 0;
-      float* rew_k = rp ? rp->R.reward + slot * NC : reward + ko * NC;
+      float* rew_k = rp ? rp->R.reward + slot * NC : nr ? nr->raw_reward + ko * NC : reward + ko * NC;
       uint8_t* cf_k = rp ? h->d_rp_cf : car_flags ? car_flags + ko * NC : nullptr;
       float* term_k = col || rp ? h->d_term : nullptr;
       const CollectBufs rrec = rp ? CollectBufs{rp->R.actions + 2 * slot * NC, nullptr, nullptr, nullptr} : CollectBufs{};
@@ -3826,7 +3852,7 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
             HIPCHK(hipMemcpyAsync(rp->R.obs + (slot * NC + r.c0) * 38, obs + r.c0 * 38, sizeof(float) * 38 * (r.c1 - r.c0),
                                   hipMemcpyDeviceToDevice, shard_stream(s)));
           if (actor && ph == 0 &&
-              launch_actions(h, policy, P, r, seed, step0 + k, o_in, h->d_ro_act, col ? &rec : rp ? &rrec : nullptr,
+              launch_actions(h, policy, P, r, seed, step0 + k, a_in, h->d_ro_act, col ? &rec : rp ? &rrec : nullptr,
                              shard_stream(s)))
             return -1;
           if (launch_step_range(h, P, r.b1 - r.b0, actor ? h->d_ro_act : nullptr, 0, actor ? -1 : policy, seed, step0 + k,
@@ -3834,7 +3860,7 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
             return -1;
           if (rp && ph == 2 && !rt && store(r, shard_stream(s))) return -1;
           // SB3's time-limit bootstrap: V(terminal obs) for the cars of truncated, not terminated envs
-          if (col && ph == 2 &&
+          if (col && ph == 2 && !nr &&
               launch_ac(h, AC_VALUE, (int)r.c0, (int)(r.c1 - r.c0), seed, step0 + k, h->d_term, nullptr, nullptr, nullptr,
                         col->timeout_values + ko * NC, ef, shard_stream(s)))
             return -1;
@@ -3843,6 +3869,15 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
       }
       if (rt && rt_after_step(h, P0, ef, o_out, stream)) return -1;
       if (rp && rt && store(shard_range(h, 0, 1), stream)) return -1;
+      if (nr)   // VecNormalize.step_wait on the step's raw outputs, then the time-limit values of the normalised terminal rows
+        for (int s = 0; s < S; ++s) {
+          const ShardRange r = shard_range(h, s, S);
+          if (norm_step_range(h, r.c0, r.c1, norm_updates(h), o_out, rew_k, ef, h->d_term, n_out, reward + ko * NC, h->d_term,
+                              shard_stream(s)) ||
+              launch_ac(h, AC_VALUE, (int)r.c0, (int)(r.c1 - r.c0), seed, step0 + k, h->d_term, nullptr, nullptr, nullptr,
+                        col->timeout_values + ko * NC, ef, shard_stream(s)))
+            return -1;
+        }
     }
     if (col)   // values [steps]: V of the observation after the last step, the bootstrap of the last record
       for (int s = 0; s < S; ++s) {
@@ -3996,9 +4031,9 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
   return 0;
 }
 
-extern "C" int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps, float* obs, float* reward,
-                              uint8_t* car_flags, uint8_t* env_flags, float* actions, float* logp, float* values,
-                              float* timeout_values, void* stream) {
+static int collect_impl(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps, float* obs, float* reward,
+                        uint8_t* car_flags, uint8_t* env_flags, float* actions, float* logp, float* values,
+                        float* timeout_values, const NormRun* nr, void* stream) {
   if (!h || !obs || !reward || !car_flags || !env_flags || !actions || !logp || !values || !timeout_values)
     return fail("null argument");
   if (steps < 1) return fail("collect: steps must be >= 1 (got %d)", steps);
@@ -4009,6 +4044,7 @@ extern "C" int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int
     return fail("the pipelined rollout has no actor-critic (policy 6): switch it off (nascar_set_rollout_pipe(h, 0))");
   if (h->fit_on) return fail("collect steps with auto-reset: switch fitness accumulation off (nascar_set_fitness(h, 0))");
   if (((uintptr_t)obs | (uintptr_t)actions) & 7) return fail("collect obs / actions must be 8-byte aligned");
+  if (nr && ((uintptr_t)nr->obs_raw & 7)) return fail("collect raw obs must be 8-byte aligned");
   if (vis_refused(h)) return -1;
   h->pristine = false;
   if (prepare(h, (hipStream_t)stream)) return -1;
@@ -4016,7 +4052,25 @@ extern "C" int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int
   HIPCHK(hipMemsetAsync(timeout_values, 0, sizeof(float) * (size_t)steps * h->N, (hipStream_t)stream));
   const CollectBufs col{actions, logp, values, timeout_values};
   return rollout_sharded(h, h->ro_streams, 6, seed, step0, steps, obs, reward, car_flags, env_flags, 1,
-                         NASCAR_TRAJ_RECORDS | NASCAR_TRAJ_OBS, (hipStream_t)stream, &col);
+                         NASCAR_TRAJ_RECORDS | NASCAR_TRAJ_OBS, (hipStream_t)stream, &col, nullptr, nr);
+}
+extern "C" int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps, float* obs, float* reward,
+                              uint8_t* car_flags, uint8_t* env_flags, float* actions, float* logp, float* values,
+                              float* timeout_values, void* stream) {
+  if (h && h->norm_on)
+    return fail("collect: normalisation is on (nascar_set_normalize): nascar_collect_normalized takes the raw observation "
+                "and the raw reward records beside the normalised ones");
+  return collect_impl(h, seed, step0, steps, obs, reward, car_flags, env_flags, actions, logp, values, timeout_values, nullptr,
+                      stream);
+}
+extern "C" int nascar_collect_normalized(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps, float* obs_raw,
+                                         float* obs, float* reward, float* raw_reward, uint8_t* car_flags, uint8_t* env_flags,
+                                         float* actions, float* logp, float* values, float* timeout_values, void* stream) {
+  if (!h || !obs_raw || !raw_reward) return fail("null argument");
+  if (!h->norm_on) return fail("collect_normalized: normalisation is off (nascar_set_normalize): use nascar_collect");
+  const NormRun nr{obs_raw, raw_reward};
+  return collect_impl(h, seed, step0, steps, obs, reward, car_flags, env_flags, actions, logp, values, timeout_values, &nr,
+                      stream);
 }
 // Off-policy collection (include/nascar.h): `steps` x (source 7 or 0 on the current obs + CarEnv.step with auto-reset) on
 // the sharded rollout, every step's transition written into the caller's ring by the shard that stepped it
@@ -4040,6 +4094,9 @@ extern "C" int nascar_collect_transitions(NascarHandle* h, int32_t source, uint6
   if (pos < 0 || pos >= replay->capacity)
     return fail("collect_transitions: pos %d outside [0, capacity = %d)", pos, replay->capacity);
   if (source == 7 && policy_ready(h, 7, obs, nullptr)) return -1;
+  if (h->norm_on)
+    return fail("collect_transitions: normalisation is on (nascar_set_normalize); off-policy normalisation happens when a "
+                "minibatch is sampled and is not provided: switch it off (nascar_set_normalize(h, NULL, stream))");
   if (h->ro_streams == 0)
     return fail("the fused rollout kernel fills no replay ring: use the sharded rollout (rollout streams >= 1)");
   if (h->ro_pipe > 0)
@@ -4083,6 +4140,152 @@ extern "C" int nascar_gae(NascarHandle* h, const float* reward, const float* val
                      timeout_values, env_flags, (float)gamma, (float)(gamma * lambda), adv, ret);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// ------------------------------------------------------------------ running normalisation (csrc/nascar_norm.h)
+// NASCAR_NORM_MUTANT (test builds only, never the product): 1 normalises before the statistics update, 2 normalises the
+// terminal rows before it, 3 never zeroes the returns -- each is seen to fail its test
+#ifndef NASCAR_NORM_MUTANT
+#define NASCAR_NORM_MUTANT 0
+#endif
+static void norm_fresh(double* st) {   // RunningMeanStd(epsilon = 1e-4): mean 0, var 1, count 1e-4
+  for (int i = 0; i < NORM_STATS; ++i) st[i] = 0.0;
+  for (int i = 0; i < NORM_OBS; ++i) st[NORM_ST_VAR + i] = 1.0;
+  st[NORM_ST_RVAR] = 1.0;
+  st[NORM_ST_COUNT] = st[NORM_ST_RCOUNT] = 1e-4;
+}
+static int norm_stats_check(const double* st) {
+  for (int i = 0; i < NORM_STATS; ++i)
+    if (!std::isfinite(st[i])) return fail("normalisation statistics: entry %d is not finite", i);
+  for (int i = 0; i < NORM_OBS; ++i)
+    if (st[NORM_ST_VAR + i] < 0.0) return fail("normalisation statistics: obs_var[%d] = %g is negative", i, st[NORM_ST_VAR + i]);
+  if (st[NORM_ST_RVAR] < 0.0) return fail("normalisation statistics: ret_var = %g is negative", st[NORM_ST_RVAR]);
+  if (!(st[NORM_ST_COUNT] > 0.0)) return fail("normalisation statistics: obs_count = %g must be positive", st[NORM_ST_COUNT]);
+  if (!(st[NORM_ST_RCOUNT] > 0.0)) return fail("normalisation statistics: ret_count = %g must be positive", st[NORM_ST_RCOUNT]);
+  return 0;
+}
+extern "C" int nascar_set_normalize(NascarHandle* h, const NascarNormalize* cfg, void* stream) {
+  if (!h) return fail("null argument");
+  if (!cfg) { h->norm_on = false; return 0; }
+  const double pos[4] = {cfg->clip_obs, cfg->clip_reward, cfg->epsilon, cfg->gamma};
+  const char* names[4] = {"clip_obs", "clip_reward", "epsilon", "gamma"};
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(pos[i]) || (i < 3 ? pos[i] <= 0.0 : pos[i] < 0.0))
+      return fail("normalize: %s = %g must be finite and %s", names[i], pos[i], i < 3 ? "positive" : ">= 0");
+  DeviceGuard on(h->cfg.device);
+  HIPCHK(on.err);
+  if (!h->d_norm) {
+    const int G = (h->N + NORM_ROWS - 1) / NORM_ROWS;
+    HIPCHK(hipMalloc(&h->d_norm, sizeof(double) * (NORM_STATS + (size_t)h->N + (size_t)G * NORM_COLS * 2)));
+    h->d_norm_ret = h->d_norm + NORM_STATS;
+    h->d_norm_part = h->d_norm_ret + h->N;
+    h->norm_groups = G;
+  }
+  if (!h->norm_on) {   // switched on: fresh statistics and returns (nascar_set_norm_stats loads others)
+    double st[NORM_STATS];
+    norm_fresh(st);
+    HIPCHK(hipMemcpyAsync(h->d_norm, st, sizeof st, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemsetAsync(h->d_norm_ret, 0, sizeof(double) * (size_t)h->N, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));   // (st is a local)
+  }
+  h->norm = *cfg;
+  h->norm_on = true;
+  return 0;
+}
+extern "C" int nascar_get_normalize(NascarHandle* h, NascarNormalize* cfg) {
+  if (!h) return fail("null argument");
+  if (cfg && h->norm_on) *cfg = h->norm;
+  return h->norm_on ? 1 : 0;
+}
+extern "C" int nascar_get_norm_stats(NascarHandle* h, double* stats, double* returns, void* stream) {
+  if (!h) return fail("null argument");
+  if (!h->norm_on) return fail("norm stats: normalisation is off (nascar_set_normalize)");
+  if (stats) HIPCHK(hipMemcpyAsync(stats, h->d_norm, sizeof(double) * NORM_STATS, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (returns)
+    HIPCHK(hipMemcpyAsync(returns, h->d_norm_ret, sizeof(double) * (size_t)h->N, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int nascar_set_norm_stats(NascarHandle* h, const double* stats, const double* returns, void* stream) {
+  if (!h || !stats) return fail("null argument");
+  if (!h->norm_on) return fail("norm stats: normalisation is off (nascar_set_normalize)");
+  if (norm_stats_check(stats)) return -1;
+  if (returns)
+    for (int n = 0; n < h->N; ++n)
+      if (!std::isfinite(returns[n])) return fail("normalisation statistics: returns[%d] is not finite", n);
+  DeviceGuard on(h->cfg.device);
+  HIPCHK(on.err);
+  HIPCHK(hipMemcpyAsync(h->d_norm, stats, sizeof(double) * NORM_STATS, hipMemcpyHostToDevice, (hipStream_t)stream));
+  if (returns)
+    HIPCHK(hipMemcpyAsync(h->d_norm_ret, returns, sizeof(double) * (size_t)h->N, hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));   // (the caller's host arrays are free on return)
+  return 0;
+}
+// the statistics update from one batch: the observation columns of obs (null: none) and, with reward, the returns
+static int norm_update(NascarHandle* h, const float* obs, const float* reward, hipStream_t s) {
+  if (!obs && !reward) return 0;
+  hipLaunchKernelGGL(norm_moments_kernel, dim3(h->norm_groups), dim3(256), 0, s, h->N, obs, reward, h->d_norm_ret,
+                     h->norm.gamma, h->d_norm_part);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(norm_update_kernel, dim3(1), dim3(64), 0, s, h->N, h->norm_groups, (const double*)h->d_norm_part,
+                     obs ? 1 : 0, reward ? 1 : 0, h->d_norm);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int norm_apply(NascarHandle* h, size_t c0, size_t c1, const float* obs_raw, const float* reward_raw,
+                      const uint8_t* env_flags, const float* term, float* obs_out, float* reward_out, float* term_out,
+                      hipStream_t s) {
+  const long long lanes = (long long)(c1 - c0) * NORM_OBS;
+  if (lanes <= 0) return 0;
+  const NormApply A{h->norm.norm_obs, h->norm.norm_reward, NASCAR_NORM_MUTANT == 3 ? 0 : 1, h->norm.clip_obs,
+                    h->norm.clip_reward, h->norm.epsilon};
+  hipLaunchKernelGGL(norm_apply_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, (int)c0, (int)c1, h->C, A,
+                     (const double*)h->d_norm, obs_raw, obs_out, term, term_out, reward_raw, reward_out, env_flags,
+                     h->d_norm_ret);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// VecNormalize.step_wait: obs_rms.update(new obs), then returns = returns * gamma + reward and ret_rms.update(returns)
+// (both inside norm_update), then normalize_obs / normalize_reward, the terminal rows of done envs under the statistics
+// as they now stand, and returns[dones] = 0 last.
+static int norm_step_range(NascarHandle* h, size_t c0, size_t c1, bool update, const float* obs_raw, const float* reward_raw,
+                           const uint8_t* env_flags, const float* term, float* obs_out, float* reward_out, float* term_out,
+                           hipStream_t s) {
+  const float* up_obs = update && h->norm.norm_obs ? obs_raw : nullptr;
+  const float* up_rew = update && h->norm.norm_reward ? reward_raw : nullptr;
+  if (NASCAR_NORM_MUTANT == 1) {
+    if (norm_apply(h, c0, c1, obs_raw, reward_raw, env_flags, term, obs_out, reward_out, term_out, s)) return -1;
+    return norm_update(h, up_obs, up_rew, s);
+  }
+  if (NASCAR_NORM_MUTANT == 2 && term) {   // (obs_out is written again below)
+    const NormApply A{h->norm.norm_obs, 0, 0, h->norm.clip_obs, h->norm.clip_reward, h->norm.epsilon};
+    hipLaunchKernelGGL(norm_apply_kernel, dim3((unsigned)(((c1 - c0) * NORM_OBS + 255) / 256)), dim3(256), 0, s, (int)c0,
+                       (int)c1, h->C, A, (const double*)h->d_norm, obs_raw, obs_out, term, term_out, (const float*)nullptr,
+                       (float*)nullptr, env_flags, h->d_norm_ret);
+    term = nullptr; term_out = nullptr;
+  }
+  if (norm_update(h, up_obs, up_rew, s)) return -1;
+  return norm_apply(h, c0, c1, obs_raw, reward_raw, env_flags, term, obs_out, reward_out, term_out, s);
+}
+static int norm_ready(const NascarHandle* h, const char* what) {
+  if (!h->norm_on) return fail("%s: normalisation is off (nascar_set_normalize)", what);
+  return 0;
+}
+extern "C" int nascar_normalize_reset(NascarHandle* h, const float* obs_raw, float* obs_out, void* stream) {
+  if (!h || !obs_raw || !obs_out) return fail("null argument");
+  if (norm_ready(h, "normalize_reset")) return -1;
+  if ((uintptr_t)obs_raw & 7) return fail("normalize_reset: obs must be 8-byte aligned");
+  HIPCHK(hipMemsetAsync(h->d_norm_ret, 0, sizeof(double) * (size_t)h->N, (hipStream_t)stream));
+  if (norm_updates(h) && h->norm.norm_obs && norm_update(h, obs_raw, nullptr, (hipStream_t)stream)) return -1;
+  return norm_apply(h, 0, h->N, obs_raw, nullptr, nullptr, nullptr, obs_out, nullptr, nullptr, (hipStream_t)stream);
+}
+extern "C" int nascar_normalize_step(NascarHandle* h, const float* obs_raw, const float* reward_raw, const uint8_t* env_flags,
+                                     const float* term_obs, float* obs_out, float* reward_out, float* term_out, void* stream) {
+  if (!h || !obs_raw || !reward_raw || !env_flags || !obs_out || !reward_out) return fail("null argument");
+  if (norm_ready(h, "normalize_step")) return -1;
+  if (!term_obs != !term_out) return fail("normalize_step: the terminal observations need both their input and their output");
+  if ((uintptr_t)obs_raw & 7) return fail("normalize_step: obs must be 8-byte aligned");
+  return norm_step_range(h, 0, h->N, norm_updates(h), obs_raw, reward_raw, env_flags, term_obs, obs_out, reward_out, term_out,
+                         (hipStream_t)stream);
 }
 
 extern "C" int nascar_get_info(NascarHandle* h, double* info, void* stream) {

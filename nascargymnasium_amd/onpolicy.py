@@ -80,6 +80,32 @@ class RolloutBatch(NamedTuple):
             yield FlatBatch(*[t[idx] for t in flat])
 
 
+class NormalizedRolloutBatch(NamedTuple):
+    """`BatchedCarEnv.collect` under `set_normalize`: RolloutBatch's fields -- obs and rewards the NORMALISED ones the
+    actor-critic and GAE saw, timeout_values V of the normalised terminal observation -- plus raw_rewards [K, E, C], the
+    step rewards before normalisation (what an episode-return monitor sums)."""
+    obs: torch.Tensor
+    actions: torch.Tensor
+    log_probs: torch.Tensor
+    values: torch.Tensor
+    rewards: torch.Tensor
+    timeout_values: torch.Tensor
+    car_flags: torch.Tensor
+    env_flags: torch.Tensor
+    advantages: torch.Tensor
+    returns: torch.Tensor
+    raw_rewards: torch.Tensor
+
+    @staticmethod
+    def spec(E, C):
+        """RolloutBatch.spec plus raw_rewards"""
+        return RolloutBatch.spec(E, C) + [("raw_rewards", torch.float32, (E, C), 0)]
+
+    steps = RolloutBatch.steps
+    flatten = RolloutBatch.flatten
+    minibatches = RolloutBatch.minibatches
+
+
 class _Extractor(torch.nn.Module):
     def __init__(self, h1, h2, v1, v2, act, vact):
         super().__init__()
