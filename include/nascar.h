@@ -289,7 +289,8 @@ int nascar_set_state(NascarHandle* h, const void* src_device, void* stream);
  *   policy 6: the sampled actor-critic of nascar_set_actor_critic -- every car draws a ~ N(mu(obs), exp(log_std)^2)
  *             from the Gaussian actor and takes min(max(a, -1), 1), the action SB3's collect_rollouts steps the env with;
  *             the draw is the one of (seed, car, step), see nascar_collect.  Fails without an actor-critic.  actions
- *             8-byte aligned.
+ *             8-byte aligned.  With a categorical actor (output 6) every car draws an action index of the env's
+ *             Discrete(5) and takes its (throttle, steering) pair, the one nascar_step(discrete = 1) steps the index with.
  *   policy 7: the explorer of nascar_set_explorer -- the sampled SAC actor, or a deterministic squashed actor with
  *             exploration noise; returns the action that steps the env.  Fails without an explorer.  actions 8-byte
  *             aligned. */
@@ -329,6 +330,18 @@ int nascar_actor_forward(NascarHandle* h, const float* obs, int32_t n, float* ac
  * Shapes: obs_dim 38, act_dim 2 and (h1, h2) one of 256-256, 256-128, 256-32, 128-128, 64-64, 32-256; every other
  * shape is rejected with a message naming it -- TD3's SB3 default [400, 300] included (the reference ships no TD3
  * checkpoint; nor is the genetic controller covered: GeneticController.control raises).
+ * The wide shape 512-512 with ReLU (learn/a2c.py:129: net_arch [512, 512], activation_fn ReLU) runs on a kernel of its own
+ *   (mlp_wide_kernel: layer 2 in chunks of four output tiles under the sixteen layer-1 tiles) for every output but 5:
+ *   nascar_set_explorer and the four-row head refuse it, and 512-512 Tanh is rejected by name.
+ * Discrete(5) (CarEnv(discrete_action_space = True)): act_dim 5, w3 [5][h2], b3 [5], the logits l of SB3's categorical
+ *   policy, with one of two outputs:
+ *          6 categorical sample: CategoricalDistribution with deterministic = False, serving nascar_set_actor_critic like
+ *            output 4 (the draw: below, with nascar_collect);
+ *          7 categorical mode: the first maximum of the logits (strict > in index order), deterministic = True; a driver
+ *            of the field like outputs 0-2 (nascar_set_car_controllers, nascar_controller_forward).
+ *   Either writes the action as the (throttle / brake, steering) pair of nascar_step's discrete path: 0 -> (0, 0),
+ *   1 -> (1, 0), 2 -> (-1, 0), 3 -> (0, -1), 4 -> (0, 1).  act_dim 5 with outputs 0-5, and outputs 6 / 7 with another
+ *   act_dim, are errors.
  * nascar_check_controller (host only, no device, h not needed): 0 if nascar_add_controller would accept the shape,
  *   activation and output, < 0 with the message otherwise.
  * nascar_add_controller: copies the weights to the device; returns the controller's id >= 0 (at most 16 per handle;
@@ -352,7 +365,8 @@ typedef struct NascarMlp {
     int32_t obs_dim, h1, h2, act_dim;
     int32_t activation;      /* 0 ReLU, 1 Tanh */
     int32_t output;          /* 0 raw, 1 clip, 2 squash; 3 value (act_dim 1), 4 sampled: nascar_set_actor_critic;
-                                5 squashed sample (act_dim 4): nascar_set_explorer */
+                                5 squashed sample (act_dim 4): nascar_set_explorer; 6 categorical sample (act_dim 5):
+                                nascar_set_actor_critic; 7 categorical mode (act_dim 5) */
     const float *w1, *b1, *w2, *b2, *w3, *b3;   /* PyTorch layouts, host */
 } NascarMlp;
 #define NASCAR_CTRL_RULE (-1)      /* policy 1 */
@@ -370,7 +384,8 @@ int nascar_update_controller(NascarHandle* h, int32_t id, const NascarMlp* mlp, 
  * nascar_set_actor_critic: the handle's actor-critic -- pi_id a sampled actor (output 4) and vf_id a critic (act_dim 1,
  *   output 3) from nascar_add_controller, and log_std [2] (host, finite; ActorCriticPolicy's state-independent log_std).
  *   log_std NULL clears it.  Calling it again with the same ids sets a new log_std (with nascar_update_controller: a
- *   learner's update).
+ *   learner's update).  pi_id may be a categorical actor (act_dim 5, output 6) instead: it has no log_std, and log_std is
+ *   not read -- but must not be NULL, which clears: pass any two floats.
  * The draw of car n at (seed, step): with key the counter key of policy 0 (seed, n, step) and mix32 its hash,
  *     u0 = ((mix32(key ^ 0x5A4D504C45) >> 8) + 1) * 2^-24  in (0, 1]
  *     u1 = (mix32(key ^ 0x3C6EF372FE94F82B) >> 8) * 2^-24   in [0, 1)
@@ -379,10 +394,21 @@ int nascar_update_controller(NascarHandle* h, int32_t id, const NascarMlp* mlp, 
  *   steps the env, and logp = sum_j (-(a_j - mu_j)^2 / (2 std_j^2) - log_std_j - log sqrt(2 pi)) is
  *   DiagGaussianDistribution.log_prob.  It depends on (seed, car index, step) alone, never on the shard, tile or lane
  *   that computes it; the two salts are used by no other action source.
+ * The draw of car n at (seed, step) of a categorical actor (output 6) with logits l_0 .. l_4: torch.multinomial cannot be
+ *   restated bit for bit, so it is an inverse CDF on one uniform of the same counter key, float32 throughout:
+ *     u = (mix32(key ^ 0x4341545F44524157) >> 8) * 2^-24  in [0, 1)         (CAT_SALT, used by no other source)
+ *     m = max_j l_j (fmaxf, index order),  e_j = expf(l_j - m),  P_0 = e_0,  P_j = P_{j-1} + e_j,  S = P_4,  t = u * S
+ *     a = the number of j in 0..3 with t >= P_j     (category 4 is the fall-through: nothing is compared with P_4)
+ *     logp = (l_a - m) - logf(S)                    Categorical(logits = l).log_prob(a)
+ *   a is the recorded action, its pair (above) steps the env: bit-identical to nascar_step(discrete = 1) on a.  It
+ *   depends on (seed, car index, step) alone.
  * nascar_collect: `steps` x (policy 6 on the current obs + CarEnv.step with auto-reset) as policy 6 of the sharded
  *   rollout, always with the per-step records and the obs trajectory of nascar_rollout (obs [steps + 1][E*C*38], record 0
  *   the current observation on entry; reward, car_flags [steps][E*C]; env_flags [steps][E]; none may be NULL), plus
- *     actions [steps][E*C][2], logp [steps][E*C]   the draws above (actions and obs 8-byte aligned)
+ *     actions [steps][E*C][2], logp [steps][E*C]   the draws above (actions and obs 8-byte aligned).  With a categorical
+ *                                                  actor `actions` points at int32 [steps][E*C], the action index a:
+ *                                                  the parameter keeps its declared type and callers cast (4-byte
+ *                                                  alignment suffices); nascar_collect_normalized likewise
  *     values [steps + 1][E*C]                      the critic on obs record k
  *     timeout_values [steps][E*C]                  the critic on the TERMINAL observation of step k for the cars of envs
  *                                                  that were truncated and not terminated there, 0 everywhere else: SB3

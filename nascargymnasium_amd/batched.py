@@ -511,26 +511,35 @@ class BatchedCarEnv:
         """Load a nascargymnasium_amd.policy.ActorCritic (load_sb3_actor_critic for the reference's PPO / A2C checkpoints,
         random_actor_critic, ActorCriticNet.export) as the handle's sampled actor-critic: policy 6 of policy_actions, and
         what `collect` runs.  Takes two of the handle's 16 controller ids; `update_actor_critic` replaces the weights
-        without taking more."""
-        from .policy import OUT_SAMPLE
-        mp, _kp = _lib.mlp_struct(ac.pi, OUT_SAMPLE)
-        mv, _kv = _lib.mlp_struct(ac.vf)
+        without taking more.  A policy.DiscreteActorCritic (load_sb3_discrete_actor_critic,
+        random_discrete_actor_critic, CategoricalActorCriticNet.export) loads the categorical actor of the env's
+        Discrete(5) the same way: `collect` then returns a DiscreteRolloutBatch."""
+        mp, mv, ls, _keep = self._ac_structs(ac)
         with torch.cuda.device(self.device):
             pi_id = _lib.check(self.L.nascar_add_controller(self.h, ctypes.byref(mp)))
             vf_id = _lib.check(self.L.nascar_add_controller(self.h, ctypes.byref(mv)))
-        ls = np.ascontiguousarray(ac.log_std, np.float32)
         _lib.check(self.L.nascar_set_actor_critic(self.h, pi_id, vf_id, ls.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
         self._ac_ids = (pi_id, vf_id)
+        self._ac_discrete = not hasattr(ac, "log_std")
+
+    @staticmethod
+    def _ac_structs(ac):
+        """(actor NascarMlp, critic NascarMlp, log_std, the arrays they point to) of an ActorCritic or a
+        DiscreteActorCritic (no log_std: the library reads none for a categorical actor, but NULL would clear)"""
+        from .policy import OUT_CATEGORICAL, OUT_SAMPLE
+        discrete = not hasattr(ac, "log_std")
+        mp, kp = _lib.mlp_struct(ac.pi, OUT_CATEGORICAL if discrete else OUT_SAMPLE)
+        mv, kv = _lib.mlp_struct(ac.vf)
+        ls = np.zeros(2, np.float32) if discrete else np.ascontiguousarray(ac.log_std, np.float32)
+        return mp, mv, ls, (kp, kv)
 
     def update_actor_critic(self, ac):
         """New weights and log_std of the same shapes and activations into the loaded actor-critic, ordered on the
-        current stream: a learner's per-iteration update.  Another shape or activation raises."""
-        from .policy import OUT_SAMPLE
+        current stream: a learner's per-iteration update.  Another shape, activation or kind (a DiscreteActorCritic into
+        a Gaussian-loaded handle, or the reverse) raises."""
         if getattr(self, "_ac_ids", None) is None:
             raise RuntimeError("update_actor_critic: no actor-critic loaded (set_actor_critic first)")
-        mp, _kp = _lib.mlp_struct(ac.pi, OUT_SAMPLE)
-        mv, _kv = _lib.mlp_struct(ac.vf)
-        ls = np.ascontiguousarray(ac.log_std, np.float32)
+        mp, mv, ls, _keep = self._ac_structs(ac)
         with torch.cuda.device(self.device):
             _lib.check(self.L.nascar_update_controller(self.h, self._ac_ids[0], ctypes.byref(mp), _stream()))
             _lib.check(self.L.nascar_update_controller(self.h, self._ac_ids[1], ctypes.byref(mv), _stream()))
@@ -548,20 +557,27 @@ class BatchedCarEnv:
         Under set_normalize the loop is the one SB3 runs around a VecNormalize: the actor-critic sees `norm_obs`, every
         step ends with `normalize_step`, GAE takes the normalised rewards, and the batch is a NormalizedRolloutBatch
         (obs and rewards normalised, raw_rewards beside them; `out` then is one too); equals `steps` x
-        (policy_actions(6, obs=norm_obs) + step(auto_reset=True, terminal_obs=True) + normalize_step(terminal_obs=True))."""
-        from .onpolicy import NormalizedRolloutBatch, RolloutBatch
+        (policy_actions(6, obs=norm_obs) + step(auto_reset=True, terminal_obs=True) + normalize_step(terminal_obs=True)).
+        With a DiscreteActorCritic loaded the actor is the categorical one: the batch is a DiscreteRolloutBatch (under
+        set_normalize a NormalizedDiscreteRolloutBatch) whose actions are the sampled int32 indices [K, E, C], which step
+        the envs as step()'s discrete actions do; `out` then is of that kind."""
+        from .onpolicy import DiscreteRolloutBatch, NormalizedDiscreteRolloutBatch, NormalizedRolloutBatch, RolloutBatch
         K = int(steps)
         if K < 1:
             raise ValueError("collect needs steps >= 1")
         E, C = self.E, self.C
-        Batch = RolloutBatch if self.normalize is None else NormalizedRolloutBatch
+        if getattr(self, "_ac_discrete", False):
+            Batch = DiscreteRolloutBatch if self.normalize is None else NormalizedDiscreteRolloutBatch
+        else:
+            Batch = RolloutBatch if self.normalize is None else NormalizedRolloutBatch
         spec = Batch.spec(E, C)
         if out is None:
             out = Batch(*[torch.empty((K + extra, *inner), dtype=dt, device=self.device)
                           for _name, dt, inner, extra in spec])
         else:
-            if len(out) != len(spec):
-                raise ValueError(f"out must be a {Batch.__name__} ({len(spec)} buffers), got {len(out)}")
+            if len(out) != len(spec) or (type(out).__name__.endswith("RolloutBatch") and not isinstance(out, Batch)):
+                raise ValueError(f"out must be a {Batch.__name__} ({len(spec)} buffers), got " +
+                                 (f"a {type(out).__name__}" if len(out) == len(spec) else str(len(out))))
             for (name, dt, inner, extra), t in zip(spec, out):
                 self._check_record_buffer(name, t, dt, inner, K + extra)
         with torch.cuda.device(self.device):
@@ -756,7 +772,8 @@ class BatchedCarEnv:
         """device-generated actions: 0 uniform U[-1,1]^2, 1 BaseController fallback driver, 2 the SAC actor, 3 the noisy
         rule driver, 4 the field of per-car controllers (set_car_controllers), 5 the genome drivers (set_genomes: the
         rule driver with per-car evolved constants; shares the rule driver's per-car state), 6 the sampled actor-critic
-        (set_actor_critic): clip(a, -1, 1) of the draw a ~ N(mu(obs), exp(log_std)) of (seed, car, step), 7 the explorer
+        (set_actor_critic): clip(a, -1, 1) of the draw a ~ N(mu(obs), exp(log_std)) of (seed, car, step) -- with a
+        DiscreteActorCritic the (throttle, steering) pair of the sampled action index (policy.DISCRETE_PAIRS) --, 7 the explorer
         (set_explorer): the sampled SAC actor, or a squashed actor with exploration noise -- the action that steps the env."""
         o = self.obs if obs is None else obs
         with torch.cuda.device(self.device):

@@ -332,10 +332,14 @@ actor_mfma32_kernel(int N, const float* __restrict__ obs, float* __restrict__ ac
 //               MLP_OUT_SAMPLE the Gaussian actor of SB3's on-policy algorithms, sampled: see mlp_sample below
 //               MLP_OUT_SQUASH_SAMPLE  SB3's SAC actor, sampled (a four-row head: mu and log_std): see mlp_explore below;
 //                              only the explorer's instantiations (EXPL) hold it
+//               MLP_OUT_CATEGORICAL  SB3's categorical actor for Discrete(5), sampled (a five-row head: the logits): see
+//                              mlp_categorical below; MLP_OUT_MODE its arg max (deterministic = True), a driver of the field.
+//                              The five-row instantiations (CAT) and mlp_wide_kernel hold them, beside outputs 0-4
 // Shapes: obs_dim 38 and act_dim 2; (h1, h2) one of MLP_SHAPES below -- 256-256 (the SAC checkpoints), 64-64 (ppo_789,
 // ppo_849), 256-128 (a2c_best_model3), and 128-128, 256-32, 32-256 for other nets; every other shape is rejected when the
 // controller is loaded (mlp_shape_ok), with a message naming it.  That includes TD3's SB3 default [400, 300]: no multiple
-// of 32, and the reference ships no TD3 checkpoint.
+// of 32, and the reference ships no TD3 checkpoint.  512-512 ReLU (MLP_WIDE_SHAPES) runs on mlp_wide_kernel below; a five-row
+// head (act_dim 5: outputs 6 and 7) on the CAT instantiations or on the wide kernel.
 // Addressing: one wave = one tile = 32 consecutive envs at ONE car slot c, so the controller is wave-uniform: row i of
 // the tile is car (env0 + i) * C + c, its observation C * 38 floats after row i - 1's, its action at [car][2].  The
 // kernel covers the env range [env0, env0 + nenv) (a rollout shard runs it on its own envs); the last tile of the range
@@ -351,15 +355,21 @@ actor_mfma32_kernel(int N, const float* __restrict__ obs, float* __restrict__ ac
 #define MLP_MAX_CTRL 16    // controllers per handle
 #define MLP_MAX_CARS 64    // car slots per env (nascar_create's limit)
 enum { MLP_RELU = 0, MLP_TANH = 1 };
-enum { MLP_OUT_RAW = 0, MLP_OUT_CLIP = 1, MLP_OUT_SQUASH = 2, MLP_OUT_VALUE = 3, MLP_OUT_SAMPLE = 4, MLP_OUT_SQUASH_SAMPLE = 5 };
+enum { MLP_OUT_RAW = 0, MLP_OUT_CLIP = 1, MLP_OUT_SQUASH = 2, MLP_OUT_VALUE = 3, MLP_OUT_SAMPLE = 4, MLP_OUT_SQUASH_SAMPLE = 5,
+       MLP_OUT_CATEGORICAL = 6, MLP_OUT_MODE = 7 };
 #define MLP_SHAPES(X) X(8, 8) X(8, 4) X(8, 1) X(4, 4) X(2, 2) X(1, 8)
+// the wide shapes (mlp_wide_kernel below; ReLU only) -- a list of their own: MLP_SHAPES is every shape that holds every head
+#define MLP_WIDE_SHAPES(X) X(16, 16)
+#define MLP_WIDE_CHUNK 4   // layer-2 output tiles per chunk of mlp_wide_kernel
+#define MLP_WIDE_KB 8      // ... and the k steps per block of its weight prefetch
 struct MlpDev {        // one loaded controller (device pointers)
   const float* w1t;    // [38][h1]  W1 transposed
   const float* b1;     // [h1]
   const float* w2t;    // [h1][h2]  W2 transposed
   const float* b2;     // [h2]
-  const float* w3;     // [2][h2]; MLP_OUT_SQUASH_SAMPLE: [4][h2], rows 0-1 mu.weight, rows 2-3 log_std.weight
-  const float* b3;     // [2]; MLP_OUT_SQUASH_SAMPLE: [4]
+  const float* w3;     // [2][h2]; MLP_OUT_SQUASH_SAMPLE: [4][h2], rows 0-1 mu.weight, rows 2-3 log_std.weight;
+                       //   MLP_OUT_CATEGORICAL / MLP_OUT_MODE: [5][h2], the logit rows
+  const float* b3;     // [2]; MLP_OUT_SQUASH_SAMPLE: [4]; MLP_OUT_CATEGORICAL / MLP_OUT_MODE: [5]
   int h1, h2, activation, output;
 };
 struct MlpLaunch {
@@ -371,8 +381,9 @@ struct MlpLaunch {
   // the on-policy outputs (nascar_collect, policy 6); rows are indexed like act, by car
   float* values;               // MLP_OUT_VALUE: [E][C]
   float* actions;              // MLP_OUT_SAMPLE: the unclipped action [E][C][2] (null: not kept); the explorer (EXPL):
-                               //   the scaled buffer action s [E][C][2] (null: not kept)
-  float* logp;                 // MLP_OUT_SAMPLE: [E][C] (null: not kept)
+                               //   the scaled buffer action s [E][C][2] (null: not kept); MLP_OUT_CATEGORICAL: the action
+                               //   index, int32 [E][C] behind this pointer (null: not kept)
+  float* logp;                 // MLP_OUT_SAMPLE, MLP_OUT_CATEGORICAL: [E][C] (null: not kept)
   const uint8_t* tflags;       // non-null: env_flags [E] of the step; only the cars of truncated, not terminated envs
   int tcars;                   //   are computed (env = car / tcars), and a tile or workgroup without one returns at once
   float log_std[2];            // MLP_OUT_SAMPLE; the explorer on an MLP_OUT_SQUASH controller: the noise sigma [2]
@@ -461,12 +472,89 @@ __device__ __forceinline__ void mlp_explore(const MlpLaunch& L, const MlpDev& W,
     u = (f32x2){unscale_action(s.x), unscale_action(s.y)};
   }
 }
+// MLP_OUT_CATEGORICAL: SB3's CategoricalDistribution over the five actions of the env's Discrete(5), sampled by an inverse
+// CDF on one mix32 draw on the car's key (salt CAT_SALT, include/nascar.h): u in [0, 1).  With l the five logits,
+//   m = max_j l_j (fmaxf, index order), e_j = expf(l_j - m), P_0 = e_0, P_j = P_{j-1} + e_j, S = P_4, t = u * S,
+//   a = #{j in 0..3 : t >= P_j}   (category 4 is the fall-through: nothing is compared with P_4)
+//   logp = (l_a - m) - logf(S)    Categorical(logits = l).log_prob(a)
+// The draw depends on (seed, car, step) alone.  MLP_OUT_MODE: the first maximum of the logits (strict > in index order).
+// Either index goes to the env as the pair of nascar_step's discrete path (model_block: _discrete_to_continuous).
+#define CAT_SALT 0x4341545F44524157ull
+__device__ __forceinline__ f32x2 discrete_pair(int a) {
+  return (f32x2){a == 1 ? 1.0f : (a == 2 ? -1.0f : 0.0f), a == 3 ? -1.0f : (a == 4 ? 1.0f : 0.0f)};
+}
+__device__ __forceinline__ void mlp_categorical(const MlpLaunch& L, size_t car, const float (&l)[5], int& a, float& logp) {
+  const float u = (float)(mix32(policy_key(L.seed, L.step, car) ^ CAT_SALT) >> 8) * (1.0f / 16777216.0f);
+  float m = l[0];
+#pragma unroll
+  for (int j = 1; j < 5; ++j) m = fmaxf(m, l[j]);
+  float d[5], P[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    d[j] = l[j] - m;
+    P[j] = j ? P[j - 1] + expf(d[j]) : expf(d[j]);
+  }
+  const float t = u * P[4];
+  a = 0;
+  float da = d[0];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (t >= P[j]) { a = j + 1; da = d[j + 1]; }   // (P is non-decreasing: the passed thresholds are a prefix)
+  logp = da - logf(P[4]);
+}
+__device__ __forceinline__ int mlp_mode(const float (&l)[5]) {
+  int a = 0;
+  float best = l[0];
+#pragma unroll
+  for (int j = 1; j < 5; ++j)
+    if (l[j] > best) { best = l[j]; a = j; }
+  return a;
+}
+// The epilogues of a five-sum head (the CAT instantiations of mlp_field_kernel, and mlp_wide_kernel): m the layer-3 sums
+// after the lane-half add; a two-row controller's rows 2-4 were zeroed in LDS and its b3 [2] is read no further.
+__device__ __forceinline__ void mlp_head5(const MlpLaunch& L, const MlpDev& W, size_t car, bool wanted, const float (&m)[5]) {
+  const float mu0 = m[0] + W.b3[0], mu1 = m[1] + W.b3[1];
+  f32x2* out = (f32x2*)&L.act[2 * car];
+  switch (W.output) {   // wave-uniform
+    case MLP_OUT_CATEGORICAL: case MLP_OUT_MODE: {
+      const float l[5] = {mu0, mu1, m[2] + W.b3[2], m[3] + W.b3[3], m[4] + W.b3[4]};
+      int a;
+      if (W.output == MLP_OUT_CATEGORICAL) {
+        float lp;
+        mlp_categorical(L, car, l, a, lp);
+        if (L.actions) ((int*)L.actions)[car] = a;
+        if (L.logp) L.logp[car] = lp;
+      } else {
+        a = mlp_mode(l);
+      }
+      *out = discrete_pair(a);
+      break;
+    }
+    case MLP_OUT_VALUE:
+      if (wanted) L.values[car] = mu0;
+      break;
+    case MLP_OUT_SAMPLE: {
+      f32x2 a; float lp;
+      mlp_sample(L, car, mu0, mu1, a, lp);
+      if (L.actions) *(f32x2*)&L.actions[2 * car] = a;
+      if (L.logp) L.logp[car] = lp;
+      *out = mlp_out<MLP_OUT_CLIP>(a.x, a.y);
+      break;
+    }
+    case MLP_OUT_SQUASH: *out = mlp_out<MLP_OUT_SQUASH>(mu0, mu1); break;
+    case MLP_OUT_CLIP: *out = mlp_out<MLP_OUT_CLIP>(mu0, mu1); break;
+    default: *out = mlp_out<MLP_OUT_RAW>(mu0, mu1); break;
+  }
+}
 // EXPL: the explorer's instantiations (policy 7), separate so that the others compile to what they were: a four-row w3 in
 // LDS and four layer-3 sums (rows 2-3 zero for a two-row controller), and mlp_explore as the only epilogue.
-template <int T1, int T2, int ACT, bool EXPL = false>
+// CAT: the five-row instantiations, separate for the same reason: a five-row w3 in LDS (rows 2-4 zero for a two-row
+// controller: a critic or a Gaussian actor that shares the launch), five layer-3 sums and mlp_head5's epilogues.
+template <int T1, int T2, int ACT, bool EXPL = false, bool CAT = false>
 __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
   constexpr int H1 = 32 * T1, H2 = 32 * T2;
-  __shared__ float s_b1[H1], s_b2[H2], s_w3[(EXPL ? 4 : 2) * H2];
+  static_assert(!(EXPL && CAT), "one head kind per instantiation");
+  __shared__ float s_b1[H1], s_b2[H2], s_w3[(EXPL ? 4 : CAT ? 5 : 2) * H2];
   const int c = L.slot_id[blockIdx.y] & 255;
   bool wanted = true;
   if (L.tflags) {   // timeout values: only the cars of envs that were truncated and not terminated at this step
@@ -484,6 +572,9 @@ __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
   if (EXPL) {
     const int n3 = (W.output == MLP_OUT_SQUASH_SAMPLE ? 4 : 2) * H2;
     for (int i = threadIdx.x; i < 4 * H2; i += 64 * AM_WAVES) s_w3[i] = i < n3 ? W.w3[i] : 0.0f;
+  } else if (CAT) {
+    const int n3 = (W.output >= MLP_OUT_CATEGORICAL ? 5 : 2) * H2;
+    for (int i = threadIdx.x; i < 5 * H2; i += 64 * AM_WAVES) s_w3[i] = i < n3 ? W.w3[i] : 0.0f;
   } else {
     for (int i = threadIdx.x; i < 2 * H2; i += 64 * AM_WAVES) s_w3[i] = W.w3[i];
   }
@@ -527,7 +618,7 @@ __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
       for (int o = 0; o < T2; ++o) acc[o] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[32 * o], b, acc[o], 0, 0, 0);
     }
   // layer 3: partial sums over this lane's half of the hidden units, then the two halves of the observation added
-  float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f;
+  float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f, m4 = 0.0f;
 #pragma unroll
   for (int t = 0; t < T2; ++t)
 #pragma unroll
@@ -536,13 +627,21 @@ __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
       const float v = mlp_act<ACT>(acc[t][q] + s_b2[u]);
       m0 = fmaf(s_w3[u], v, m0);
       m1 = fmaf(s_w3[H2 + u], v, m1);
-      if (EXPL) {
+      if (EXPL || CAT) {
         m2 = fmaf(s_w3[2 * H2 + u], v, m2);
         m3 = fmaf(s_w3[3 * H2 + u], v, m3);
       }
+      if (CAT) m4 = fmaf(s_w3[4 * H2 + u], v, m4);
     }
   m0 += __shfl_xor(m0, 32);
   m1 += __shfl_xor(m1, 32);
+  if (CAT) {
+    m2 += __shfl_xor(m2, 32);
+    m3 += __shfl_xor(m3, 32);
+    m4 += __shfl_xor(m4, 32);
+    if (h == 0 && i < L.nenv) mlp_head5(L, W, car, wanted, {m0, m1, m2, m3, m4});
+    return;
+  }
   if (EXPL) {
     m2 += __shfl_xor(m2, 32);
     m3 += __shfl_xor(m3, 32);
@@ -574,6 +673,122 @@ __global__ void __launch_bounds__(64 * AM_WAVES) mlp_field_kernel(MlpLaunch L) {
       default: *out = mlp_out<MLP_OUT_RAW>(mu0, mu1); break;
     }
   }
+}
+
+// ------------------------------------------------------------------ the wide MLP: 512-512 ReLU (learn/a2c.py's net_arch)
+// mlp_field_kernel<T1, T2> keeps 16 (T1 + T2) accumulator registers: 512 at 16 + 16, the whole register file of a lane.
+// mlp_wide_kernel holds the 16 layer-1 tiles (256 registers: layer 2's B operands) and runs layer 2 in chunks of TC output
+// tiles, folding each chunk's layer-3 partial sums into the five sums before the next chunk reuses the accumulators.  The
+// result is what a monolithic <16, 16> would compute: a chunk's accumulators see their k steps in the same order (t, then
+// q), the bias is added after the accumulation, and the chunks are folded in ascending order, so each sum's fmaf chain
+// runs over ascending u per lane half.  Addressing, the ragged last tile and the tflags early-out are mlp_field_kernel's.
+// Heads: every epilogue of mlp_head5 (outputs 0-4, 6, 7); no explorer, no Tanh (tanhf as a call under ~330 live registers).
+template <int T1, int T2, int TC>
+__global__ void __launch_bounds__(64 * AM_WAVES) mlp_wide_kernel(MlpLaunch L) {
+  constexpr int H1 = 32 * T1, H2 = 32 * T2;
+  static_assert(T2 % TC == 0, "whole chunks");
+  __shared__ float s_b1[H1], s_b2[H2], s_w3[5 * H2];
+  const int c = L.slot_id[blockIdx.y] & 255;
+  bool wanted = true;
+  if (L.tflags) {   // timeout values: only the cars of envs that were truncated and not terminated at this step
+    const int it = (blockIdx.x * AM_WAVES + (threadIdx.x >> 6)) * 32 + (threadIdx.x & 31);
+    wanted = false;
+    if (it < L.nenv) {
+      const uint8_t f = L.tflags[((size_t)(L.env0 + it) * L.C + c) / L.tcars];
+      wanted = (f & 2) && !(f & 1);
+    }
+    if (!__syncthreads_or(wanted)) return;   // block-uniform: nothing has been loaded yet
+  }
+  const MlpDev W = L.table[L.slot_id[blockIdx.y] >> 8];
+  for (int i = threadIdx.x; i < H1; i += 64 * AM_WAVES) s_b1[i] = W.b1[i];
+  for (int i = threadIdx.x; i < H2; i += 64 * AM_WAVES) s_b2[i] = W.b2[i];
+  const int n3 = (W.output >= MLP_OUT_CATEGORICAL ? 5 : 2) * H2;   // a two-row head is not read past its rows
+  for (int i = threadIdx.x; i < 5 * H2; i += 64 * AM_WAVES) s_w3[i] = i < n3 ? W.w3[i] : 0.0f;
+  __syncthreads();
+  const int l = threadIdx.x & 63, r = l & 31, h = l >> 5;
+  const int tile = blockIdx.x * AM_WAVES + (threadIdx.x >> 6);
+  const int i0 = tile * 32;
+  if (i0 >= L.nenv) return;
+  if (L.tflags && !__any(wanted)) return;   // wave-uniform
+  const int i = i0 + r;
+  const size_t car = (size_t)(L.env0 + (i < L.nenv ? i : L.nenv - 1)) * L.C + c;
+  const float* xr = L.obs + car * ACT_OBS;
+  f32x16 hid[T1];   // layer-1 accumulators, then relu(H1 + b1) in place: layer 2's B operands, live through every chunk
+  // in two halves of T1 / 2 tiles (each tile's k order is unchanged): 16 T1 accumulators at once fill the accumulator
+  // file, and their activation in place then costs spills
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+#pragma unroll
+    for (int t = half * (T1 / 2); t < (half + 1) * (T1 / 2); ++t) hid[t] = (f32x16){};
+#pragma unroll
+    for (int s = 0; s < ACT_OBS / 2; ++s) {
+      const float b = xr[2 * s + h];
+      const float* w = W.w1t + (size_t)(2 * s + h) * H1 + r;
+#pragma unroll
+      for (int t = half * (T1 / 2); t < (half + 1) * (T1 / 2); ++t)
+        hid[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[32 * t], b, hid[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = half * (T1 / 2); t < (half + 1) * (T1 / 2); ++t)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int u = 32 * t + (q & 3) + 8 * (q >> 2) + 4 * h;
+        hid[t][q] = fmaxf(hid[t][q] + s_b1[u], 0.0f);
+      }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  float m[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+  for (int ch = 0; ch < T2 / TC; ++ch) {   // a real loop: one chunk's code (16 T1 TC MFMAs), not T2 / TC copies of it
+    f32x16 acc[TC];
+#pragma unroll
+    for (int o = 0; o < TC; ++o) acc[o] = (f32x16){};
+    // k step k = 16 t + q takes hid[t][q], hidden unit u(k), in mlp_field_kernel's order.  The A operands (W2^T rows,
+    // L2-resident) are fetched one block of KB k steps ahead of their use, and nothing is scheduled across a block's end:
+    // with hid filling the vector registers the scheduler left to itself hoists no load, and every k step waits a full
+    // L2 latency (measured at 8192 x 10: collect 3.79 ms per step with the plain loop, 0.99 ms with this one; KB = 16
+    // measured the same as 8)
+    const float* wc = W.w2t + 32 * TC * ch + r;
+    constexpr int KB = MLP_WIDE_KB, NB = 16 * T1 / KB;
+#define WIDE_U(k) (32 * ((k) >> 4) + ((k) & 3) + 8 * (((k) & 15) >> 2) + 4 * h)
+    float wn[KB * TC];
+#pragma unroll
+    for (int j = 0; j < KB; ++j)
+#pragma unroll
+      for (int o = 0; o < TC; ++o) wn[j * TC + o] = wc[(size_t)WIDE_U(j) * H2 + 32 * o];
+#pragma unroll
+    for (int blk = 0; blk < NB; ++blk) {
+      float wcur[KB * TC];
+#pragma unroll
+      for (int j = 0; j < KB * TC; ++j) wcur[j] = wn[j];
+      if (blk + 1 < NB) {
+#pragma unroll
+        for (int j = 0; j < KB; ++j)
+#pragma unroll
+          for (int o = 0; o < TC; ++o) wn[j * TC + o] = wc[(size_t)WIDE_U(KB * (blk + 1) + j) * H2 + 32 * o];
+      }
+#pragma unroll
+      for (int j = 0; j < KB; ++j) {
+        const float b = hid[(KB * blk + j) >> 4][(KB * blk + j) & 15];
+#pragma unroll
+        for (int o = 0; o < TC; ++o) acc[o] = __builtin_amdgcn_mfma_f32_32x32x2f32(wcur[j * TC + o], b, acc[o], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#undef WIDE_U
+#pragma unroll
+    for (int o = 0; o < TC; ++o)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int u = 32 * (TC * ch + o) + (q & 3) + 8 * (q >> 2) + 4 * h;
+        const float v = fmaxf(acc[o][q] + s_b2[u], 0.0f);
+#pragma unroll
+        for (int j = 0; j < 5; ++j) m[j] = fmaf(s_w3[j * H2 + u], v, m[j]);
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < 5; ++j) m[j] += __shfl_xor(m[j], 32);
+  if (h == 0 && i < L.nenv) mlp_head5(L, W, car, wanted, m);
 }
 
 // ------------------------------------------------------------------ GAE (nascar_gae, nascar_collect)

@@ -3838,7 +3838,9 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
         return 0;
       };
       // nascar_collect: a ~ N(mu, std) and V on the step's observation into actions / logp / values [k]; clip(a) drives the step
-      const CollectBufs rec = col ? CollectBufs{col->actions + 2 * ko * NC, col->logp + ko * NC, col->values + ko * NC, nullptr}
+      // (a categorical actor's action record is one int32 index per car behind the same pointer, not a float pair)
+      const size_t act_w = col && h->ctrl[h->ac_pi].output == MLP_OUT_CATEGORICAL ? 1 : 2;
+      const CollectBufs rec = col ? CollectBufs{col->actions + act_w * ko * NC, col->logp + ko * NC, col->values + ko * NC, nullptr}
                                   : CollectBufs{};
       // phase-major enqueue (every shard's model launch, then every shard's logic, then sensors): each stream's
       // order is unchanged, but a shard's first launch of the call is queued ~6 us (one launch) after the previous
@@ -4043,7 +4045,9 @@ static int collect_impl(NascarHandle* h, uint64_t seed, int64_t step0, int32_t s
   if (h->ro_pipe > 0)
     return fail("the pipelined rollout has no actor-critic (policy 6): switch it off (nascar_set_rollout_pipe(h, 0))");
   if (h->fit_on) return fail("collect steps with auto-reset: switch fitness accumulation off (nascar_set_fitness(h, 0))");
-  if (((uintptr_t)obs | (uintptr_t)actions) & 7) return fail("collect obs / actions must be 8-byte aligned");
+  const bool cat = h->ctrl[h->ac_pi].output == MLP_OUT_CATEGORICAL;   // actions: int32 [steps][E*C], the action index
+  if (((uintptr_t)obs | (cat ? 0 : (uintptr_t)actions)) & 7) return fail("collect obs / actions must be 8-byte aligned");
+  if ((uintptr_t)actions & 3) return fail("collect actions must be 4-byte aligned");
   if (nr && ((uintptr_t)nr->obs_raw & 7)) return fail("collect raw obs must be 8-byte aligned");
   if (vis_refused(h)) return -1;
   h->pristine = false;
@@ -4680,29 +4684,51 @@ static bool mlp_shape_ok(int h1, int h2) {
 #undef X
   return false;
 }
+static bool mlp_wide_ok(int h1, int h2) {   // the shapes of mlp_wide_kernel: ReLU, no explorer
+#define X(A, B) if (h1 == 32 * (A) && h2 == 32 * (B)) return true;
+  MLP_WIDE_SHAPES(X)
+#undef X
+  return false;
+}
+static bool mlp_cat(int output) { return output == MLP_OUT_CATEGORICAL || output == MLP_OUT_MODE; }
 extern "C" int nascar_check_controller(const NascarMlp* m) {
   if (!m) return fail("null argument");
   const bool value = m->act_dim == 1 && m->output == MLP_OUT_VALUE;   // a critic: one output, the value
   const bool head4 = m->act_dim == 4 && m->output == MLP_OUT_SQUASH_SAMPLE;   // the sampled SAC actor: mu and log_std rows
-  if (m->obs_dim != ACT_OBS || (m->act_dim != ACT_OUT && !value && !head4) || !mlp_shape_ok(m->h1, m->h2))
+  const bool rows5 = m->act_dim == 5;   // the categorical actor of Discrete(5): five logit rows (outputs 6 and 7 alone)
+  const bool wide = mlp_wide_ok(m->h1, m->h2);
+  if (m->obs_dim != ACT_OBS || (m->act_dim != ACT_OUT && !value && !head4 && !rows5) || (!mlp_shape_ok(m->h1, m->h2) && !wide))
     return fail("controller shape %d -> %d -> %d -> %d unsupported: need obs 38, 2 actions and hidden layers 256-256, 256-128, "
-                "256-32, 128-128, 64-64 or 32-256 (the SB3 checkpoints the reference ships; TD3's [400, 300] is not among them)",
+                "256-32, 128-128, 64-64 or 32-256 (the SB3 checkpoints the reference ships; TD3's [400, 300] is not among them), "
+                "or 512-512 with ReLU; 5 logits with output 6 or 7",
                 m->obs_dim, m->h1, m->h2, m->act_dim);
   if (m->activation != MLP_RELU && m->activation != MLP_TANH)
     return fail("controller activation must be 0 (ReLU) or 1 (Tanh), got %d", m->activation);
+  if (wide && m->activation != MLP_RELU)
+    return fail("controller shape %d -> %d -> %d -> %d with Tanh unsupported: the wide kernel holds 512-512 ReLU; 512-512 Tanh is "
+                "not among its shapes", m->obs_dim, m->h1, m->h2, m->act_dim);
+  if (wide && m->output == MLP_OUT_SQUASH_SAMPLE)
+    return fail("controller shape %d -> %d -> %d -> %d: the wide 512-512 kernel holds no explorer head (output 5, nascar_set_explorer)",
+                m->obs_dim, m->h1, m->h2, m->act_dim);
+  if (rows5 && m->output >= MLP_OUT_RAW && m->output <= MLP_OUT_SQUASH_SAMPLE)
+    return fail("controller output %d takes no five-row head: act_dim 5 (the logits of Discrete(5)) needs output 6 (categorical "
+                "sample) or 7 (categorical mode)", m->output);
   if (m->output == MLP_OUT_VALUE && !value) return fail("controller output 3 (value) needs act_dim 1, got %d", m->act_dim);
   if (m->output == MLP_OUT_SQUASH_SAMPLE && !head4)
     return fail("controller output 5 (squashed sample) needs act_dim 4 (w3 rows: mu, then log_std), got %d", m->act_dim);
-  if (m->output != MLP_OUT_RAW && m->output != MLP_OUT_CLIP && m->output != MLP_OUT_SQUASH && m->output != MLP_OUT_VALUE &&
-      m->output != MLP_OUT_SAMPLE && m->output != MLP_OUT_SQUASH_SAMPLE)
-    return fail("controller output must be 0 (raw), 1 (clip), 2 (squash), 3 (value, act_dim 1), 4 (sampled) or 5 (squashed "
-                "sample, act_dim 4), got %d", m->output);
+  if (mlp_cat(m->output) && !rows5)
+    return fail("controller output must be 0 (raw), 1 (clip), 2 (squash) or 4 (sampled) for act_dim %d: output %d (categorical "
+                "%s) needs act_dim 5 (w3 rows: the five logits)", m->act_dim, m->output,
+                m->output == MLP_OUT_MODE ? "mode" : "sample");
+  if (m->output < MLP_OUT_RAW || m->output > MLP_OUT_MODE)
+    return fail("controller output must be 0 (raw), 1 (clip), 2 (squash), 3 (value, act_dim 1), 4 (sampled), 5 (squashed "
+                "sample, act_dim 4), 6 (categorical sample, act_dim 5) or 7 (categorical mode, act_dim 5), got %d", m->output);
   return 0;
 }
 // A controller's device image in host floats: W1^T [38][h1], b1, W2^T [h1][h2], b2, W3 [2][h2], b3 [2] (the transposes
 // give mlp_field_kernel's A operands coalesced rows); a critic's value head is padded with a zero second row
-// (the sampled SAC actor's head has four rows: rows3 = 4)
-static int mlp_rows3(int output) { return output == MLP_OUT_SQUASH_SAMPLE ? 4 : 2; }
+// (the sampled SAC actor's head has four rows: rows3 = 4; the categorical actor's five)
+static int mlp_rows3(int output) { return output == MLP_OUT_SQUASH_SAMPLE ? 4 : mlp_cat(output) ? 5 : 2; }
 static size_t mlp_floats(int H1, int H2, int rows3) {
   return (size_t)ACT_OBS * H1 + H1 + (size_t)H1 * H2 + H2 + rows3 * (size_t)H2 + rows3;
 }
@@ -4779,11 +4805,14 @@ extern "C" int nascar_set_actor_critic(NascarHandle* h, int32_t pi_id, int32_t v
   const int n = (int)h->ctrl.size();
   if (pi_id < 0 || pi_id >= n || vf_id < 0 || vf_id >= n)
     return fail("actor-critic: unknown controller id (pi %d, vf %d; %d loaded with nascar_add_controller)", pi_id, vf_id, n);
-  if (h->ctrl[pi_id].output != MLP_OUT_SAMPLE) return fail("actor-critic: controller %d is no sampled actor (output 4)", pi_id);
+  const bool cat = h->ctrl[pi_id].output == MLP_OUT_CATEGORICAL;   // the categorical actor has no log_std: not read
+  if (h->ctrl[pi_id].output != MLP_OUT_SAMPLE && !cat)
+    return fail("actor-critic: controller %d is no sampled actor (output 4, or 6 for the categorical one)", pi_id);
   if (h->ctrl[vf_id].output != MLP_OUT_VALUE) return fail("actor-critic: controller %d is no critic (act_dim 1, output 3)", vf_id);
-  if (!std::isfinite(log_std[0]) || !std::isfinite(log_std[1]))
+  if (!cat && (!std::isfinite(log_std[0]) || !std::isfinite(log_std[1])))
     return fail("actor-critic: log_std (%g, %g) is not finite", log_std[0], log_std[1]);
-  h->ac_pi = pi_id; h->ac_vf = vf_id; h->ac_log_std[0] = log_std[0]; h->ac_log_std[1] = log_std[1];
+  h->ac_pi = pi_id; h->ac_vf = vf_id;
+  h->ac_log_std[0] = cat ? 0.0f : log_std[0]; h->ac_log_std[1] = cat ? 0.0f : log_std[1];
   h->ac_set = true;
   return 0;
 }
@@ -4791,7 +4820,8 @@ extern "C" int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl) 
   if (!h) return fail("null argument");
   if (!ctrl) { h->field_set = false; return 0; }
   for (int c = 0; c < h->C; ++c)
-    if (ctrl[c] >= 0 && ctrl[c] < (int)h->ctrl.size() && h->ctrl[ctrl[c]].output >= MLP_OUT_VALUE)
+    if (ctrl[c] >= 0 && ctrl[c] < (int)h->ctrl.size() && h->ctrl[ctrl[c]].output >= MLP_OUT_VALUE &&
+        h->ctrl[ctrl[c]].output != MLP_OUT_MODE)   // (the categorical mode, output 7, is a driver like outputs 0-2)
       return fail("car slot %d: controller %d is a critic or a sampled actor (nascar_set_actor_critic, nascar_set_explorer), "
                   "no driver of the field", c, ctrl[c]);
   for (int c = 0; c < h->C; ++c)
@@ -4806,8 +4836,31 @@ extern "C" int nascar_set_car_controllers(NascarHandle* h, const int32_t* ctrl) 
 // One launch of mlp_field_kernel's instantiation for K's (h1, h2, activation) over a batch of n rows (a wave per 32) and
 // ny grid-y entries (L.slot_id); an error if there is none (shapes are checked at load)
 // explore: the explorer's instantiations (policy 7: the exploring epilogues, a four-row head)
-static int mlp_launch(const MlpDev& K, int n, int ny, hipStream_t s, const MlpLaunch& L, bool explore = false) {
+// head5: the five-row instantiations (a categorical controller is among the launch's); the wide kernel holds every
+// head but the explorer's
+static int mlp_launch(const MlpDev& K, int n, int ny, hipStream_t s, const MlpLaunch& L, bool explore = false,
+                      bool head5 = false) {
   const dim3 grid(((n + 31) / 32 + AM_WAVES - 1) / AM_WAVES, ny);
+#define X(A, B)                                                                                                  \
+  if (K.h1 == 32 * (A) && K.h2 == 32 * (B)) {                                                                    \
+    if (explore || K.activation != MLP_RELU)                                                                     \
+      return fail("no wide kernel for controller shape %d-%d with %s", K.h1, K.h2, explore ? "the explorer" : "Tanh"); \
+    hipLaunchKernelGGL((mlp_wide_kernel<A, B, MLP_WIDE_CHUNK>), grid, dim3(64 * AM_WAVES), 0, s, L);              \
+    HIPCHK(hipGetLastError());                                                                                   \
+    return 0;                                                                                                    \
+  }
+  MLP_WIDE_SHAPES(X)
+#undef X
+#define X(A, B)                                                                                                  \
+  if (K.h1 == 32 * (A) && K.h2 == 32 * (B) && head5) {                                                           \
+    if (K.activation == MLP_RELU)                                                                                \
+      hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_RELU, false, true>), grid, dim3(64 * AM_WAVES), 0, s, L);    \
+    else hipLaunchKernelGGL((mlp_field_kernel<A, B, MLP_TANH, false, true>), grid, dim3(64 * AM_WAVES), 0, s, L); \
+    HIPCHK(hipGetLastError());                                                                                   \
+    return 0;                                                                                                    \
+  }
+  MLP_SHAPES(X)
+#undef X
 #define X(A, B)                                                                                                  \
   if (K.h1 == 32 * (A) && K.h2 == 32 * (B)) {                                                                    \
     if (explore && K.activation == MLP_RELU)                                                                     \
@@ -4840,14 +4893,16 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
     MlpLaunch L{};
     L.table = h->d_ctrl; L.obs = obs; L.act = act; L.env0 = env0; L.nenv = nenv; L.C = C;
     int ns = 0;
+    bool head5 = false;   // a categorical-mode driver among the launch's controllers: the five-row instantiation for all
     for (int d = c; d < C; ++d) {
       if (h->field[d] < 0 || done[d]) continue;
       const MlpDev& D = h->ctrl[h->field[d]];
       if (D.h1 != K.h1 || D.h2 != K.h2 || D.activation != K.activation) continue;
       L.slot_id[ns++] = d | (h->field[d] << 8);
+      head5 |= mlp_cat(D.output);
       done[d] = true;
     }
-    if (mlp_launch(K, nenv, ns, s, L)) return -1;
+    if (mlp_launch(K, nenv, ns, s, L, false, head5)) return -1;
   }
   const int n0 = env0 * C, n1 = (env0 + nenv) * C;
   if (genome_slots) {
@@ -4879,13 +4934,16 @@ static int launch_ac(NascarHandle* h, int what, int c0, int n, uint64_t seed, in
   L.log_std[0] = h->ac_log_std[0]; L.log_std[1] = h->ac_log_std[1]; L.seed = seed; L.step = step;
   const bool both = (what & AC_SAMPLE) && (what & AC_VALUE);
   const bool shared = PI.h1 == VF.h1 && PI.h2 == VF.h2 && PI.activation == VF.activation;
+  // a categorical actor (`actions` then holds int32 indices, one per car) runs the five-row instantiation; a critic that
+  // shares its launch rides in it (its two-row head is zero-padded in LDS, not over-read)
+  const bool head5 = mlp_cat(PI.output);
   if (both && shared) {
     L.slot_id[0] = h->ac_pi << 8; L.slot_id[1] = h->ac_vf << 8;
-    return mlp_launch(PI, n, 2, s, L);
+    return mlp_launch(PI, n, 2, s, L, false, head5);
   }
   if (what & AC_SAMPLE) {
     L.slot_id[0] = h->ac_pi << 8;
-    if (mlp_launch(PI, n, 1, s, L)) return -1;
+    if (mlp_launch(PI, n, 1, s, L, false, head5)) return -1;
   }
   if (what & AC_VALUE) {
     L.slot_id[0] = h->ac_vf << 8;
@@ -4914,6 +4972,9 @@ extern "C" int nascar_set_explorer(NascarHandle* h, int32_t id, const float* sig
     return fail("explorer: controller %d has output %d; need 5 (the sampled SAC actor) or 2 (squash, with a noise sigma)", id, out);
   if (out == MLP_OUT_SQUASH_SAMPLE && sigma)
     return fail("explorer: controller %d is a sampled SAC actor (output 5): it takes no noise sigma (pass NULL)", id);
+  if (mlp_wide_ok(h->ctrl[id].h1, h->ctrl[id].h2))
+    return fail("explorer: controller %d is %d-%d: the wide kernel holds no exploring epilogue", id, h->ctrl[id].h1,
+                h->ctrl[id].h2);
   float s0 = 0.0f, s1 = 0.0f;
   if (sigma) { s0 = sigma[0]; s1 = sigma[1]; }
   if (!std::isfinite(s0) || !std::isfinite(s1) || s0 < 0.0f || s1 < 0.0f)
@@ -4925,7 +4986,7 @@ extern "C" int nascar_controller_forward(NascarHandle* h, int32_t id, const floa
                                          void* stream) {
   if (!h || n < 0) return fail("bad argument");
   if (id < 0 || id >= (int)h->ctrl.size()) return fail("unknown controller id %d (%d loaded)", id, (int)h->ctrl.size());
-  if (h->ctrl[id].output >= MLP_OUT_VALUE)
+  if (h->ctrl[id].output >= MLP_OUT_VALUE && h->ctrl[id].output != MLP_OUT_MODE)
     return fail("controller %d is a critic or a sampled actor: it runs as policy 6 (nascar_set_actor_critic) or 7 "
                 "(nascar_set_explorer)", id);
   if (n == 0) return 0;   // an empty batch has no buffers: its pointers may be null
@@ -4935,7 +4996,7 @@ extern "C" int nascar_controller_forward(NascarHandle* h, int32_t id, const floa
   MlpLaunch L{};   // a flat batch: n envs of one car slot
   L.table = h->d_ctrl; L.obs = obs; L.act = actions; L.env0 = 0; L.nenv = n; L.C = 1;
   L.slot_id[0] = id << 8;
-  return mlp_launch(K, n, 1, (hipStream_t)stream, L);
+  return mlp_launch(K, n, 1, (hipStream_t)stream, L, false, mlp_cat(K.output));
 }
 
 extern "C" int nascar_debug_sincosf(const float* x, float* s, float* c, int32_t n, void* stream) {

@@ -159,3 +159,99 @@ class ActorCriticNet(torch.nn.Module):
         mu, values = self.forward(obs)
         dist = torch.distributions.Normal(mu, torch.ones_like(mu) * self.log_std.exp())
         return values, dist.log_prob(actions.reshape(-1, 2)).sum(dim=1), dist.entropy().sum(dim=1)
+
+
+# ------------------------------------------------------------------ the categorical actor-critic (Discrete(5))
+class DiscreteRolloutBatch(NamedTuple):
+    """`BatchedCarEnv.collect` with a policy.DiscreteActorCritic: RolloutBatch's fields with actions int32 [K, E, C], the
+    sampled action index in 0..4 (what SB3's buffer keeps for a Discrete space; the envs were stepped with it)."""
+    obs: torch.Tensor
+    actions: torch.Tensor
+    log_probs: torch.Tensor
+    values: torch.Tensor
+    rewards: torch.Tensor
+    timeout_values: torch.Tensor
+    car_flags: torch.Tensor
+    env_flags: torch.Tensor
+    advantages: torch.Tensor
+    returns: torch.Tensor
+
+    @staticmethod
+    def spec(E, C):
+        """RolloutBatch.spec with the actions record int32 [E, C]"""
+        return [("actions", torch.int32, (E, C), 0) if s[0] == "actions" else s for s in RolloutBatch.spec(E, C)]
+
+    steps = RolloutBatch.steps
+    minibatches = RolloutBatch.minibatches
+
+    def flatten(self) -> FlatBatch:
+        K = self.steps
+        return FlatBatch(self.obs[:K].reshape(-1, OBS_DIM), self.actions.reshape(-1), self.log_probs.reshape(-1),
+                         self.values[:K].reshape(-1), self.advantages.reshape(-1), self.returns.reshape(-1))
+
+
+class NormalizedDiscreteRolloutBatch(NamedTuple):
+    """DiscreteRolloutBatch under `set_normalize`: obs and rewards normalised, raw_rewards beside them (as
+    NormalizedRolloutBatch)."""
+    obs: torch.Tensor
+    actions: torch.Tensor
+    log_probs: torch.Tensor
+    values: torch.Tensor
+    rewards: torch.Tensor
+    timeout_values: torch.Tensor
+    car_flags: torch.Tensor
+    env_flags: torch.Tensor
+    advantages: torch.Tensor
+    returns: torch.Tensor
+    raw_rewards: torch.Tensor
+
+    @staticmethod
+    def spec(E, C):
+        """DiscreteRolloutBatch.spec plus raw_rewards"""
+        return DiscreteRolloutBatch.spec(E, C) + [("raw_rewards", torch.float32, (E, C), 0)]
+
+    steps = RolloutBatch.steps
+    flatten = DiscreteRolloutBatch.flatten
+    minibatches = RolloutBatch.minibatches
+
+
+class CategoricalActorCriticNet(torch.nn.Module):
+    """SB3's ActorCriticPolicy for Box(38) -> Discrete(5) with an MlpExtractor of two hidden layers per branch, with SB3's
+    parameter names (mlp_extractor.policy_net.{0,2}, mlp_extractor.value_net.{0,2}, action_net = Linear(h2, 5), value_net;
+    no log_std): its state_dict loads into, and from, an SB3 policy of the same net_arch."""
+
+    def __init__(self, ac: P.DiscreteActorCritic):
+        super().__init__()
+        acts = {P.RELU: torch.nn.ReLU, P.TANH: torch.nn.Tanh}
+        self.activation, self.vf_activation = int(ac.pi.activation), int(ac.vf.activation)
+        self.mlp_extractor = _Extractor(ac.pi.h1, ac.pi.h2, ac.vf.h1, ac.vf.h2, acts[self.activation], acts[self.vf_activation])
+        self.action_net = torch.nn.Linear(ac.pi.h2, P.N_DISCRETE)
+        self.value_net = torch.nn.Linear(ac.vf.h2, 1)
+        self.load_record(ac)
+
+    _layers = ActorCriticNet._layers
+
+    def load_record(self, ac: P.DiscreteActorCritic):
+        with torch.no_grad():
+            for layers, arrays in zip(self._layers(), (ac.pi.arrays, ac.vf.arrays)):
+                for i, lin in enumerate(layers):
+                    lin.weight.copy_(torch.from_numpy(np.asarray(arrays[2 * i])))
+                    lin.bias.copy_(torch.from_numpy(np.asarray(arrays[2 * i + 1])))
+
+    def export(self) -> P.DiscreteActorCritic:
+        """the current parameters as a float32 DiscreteActorCritic record (for BatchedCarEnv.update_actor_critic)"""
+        pi, vf = [[a.detach().float().cpu().numpy() for lin in layers for a in (lin.weight, lin.bias)]
+                  for layers in self._layers()]
+        return P.make_discrete_actor_critic(pi, vf, self.activation, "actor_critic", self.vf_activation)
+
+    def forward(self, obs):
+        """(logits [n, 5], values [n, 1])"""
+        x = obs.reshape(-1, OBS_DIM)
+        return self.action_net(self.mlp_extractor.policy_net(x)), self.value_net(self.mlp_extractor.value_net(x))
+
+    def evaluate_actions(self, obs, actions):
+        """ActorCriticPolicy.evaluate_actions: (values [n, 1], log_prob [n], entropy [n]) of the action indices `actions` [n]
+        under the current policy on `obs` [n, 38] (CategoricalDistribution: torch's Categorical(logits=...))."""
+        logits, values = self.forward(obs)
+        dist = torch.distributions.Categorical(logits=logits)
+        return values, dist.log_prob(actions.reshape(-1).long()), dist.entropy()

@@ -64,6 +64,8 @@ RELU, TANH = 0, 1                       # NascarMlp.activation
 OUT_RAW, OUT_CLIP, OUT_SQUASH = 0, 1, 2  # NascarMlp.output
 OUT_VALUE, OUT_SAMPLE = 3, 4            # a critic's value head / the sampled Gaussian actor (policy 6: ActorCritic)
 MLP_SHAPES = ((256, 256), (256, 128), (256, 32), (128, 128), (64, 64), (32, 256))   # csrc/nascar_actor.h MLP_SHAPES
+WIDE_SHAPES = ((512, 512),)             # csrc/nascar_actor.h MLP_WIDE_SHAPES (mlp_wide_kernel): ReLU only, no explorer head
+OUT_CATEGORICAL, OUT_MODE = 6, 7        # the categorical actor of Discrete(5), sampled (DiscreteActorCritic) / its arg max
 SAC_KEYS = ACTOR_KEYS
 AC_KEYS = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias", "mlp_extractor.policy_net.2.weight",
            "mlp_extractor.policy_net.2.bias", "action_net.weight", "action_net.bias")
@@ -73,6 +75,8 @@ class Controller(NamedTuple):
     """One MLP controller: PyTorch layouts w1 [h1, 38], b1 [h1], w2 [h2, h1], b2 [h2], w3 [2, h2], b3 [2] (float32).
     activation: RELU / TANH on both hidden layers.  output: OUT_RAW (mu = W3 h + b3), OUT_CLIP (np.clip(mu, -1, 1):
     SB3 predict for an unsquashed Box policy, PPO / A2C) or OUT_SQUASH (tanh(mu) then unscale_action: SAC).
+    A five-row head (w3 [5, h2], b3 [5]: the logits of the env's Discrete(5)) takes OUT_CATEGORICAL (sampled: the actor of a
+    DiscreteActorCritic) or OUT_MODE (the arg max, SB3's deterministic predict: a driver of the field).
     kind: "sac", "actor_critic" or "random"."""
     w1: np.ndarray
     b1: np.ndarray
@@ -98,11 +102,13 @@ def make_controller(arrays, activation: int, output: int, kind: str = "random") 
     if w1.ndim != 2 or w2.ndim != 2 or w3.ndim != 2:
         raise ValueError("controller weights must be 2-D")
     h1, h2 = int(w1.shape[0]), int(w2.shape[0])
-    want = ((h1, 38), (h1,), (h2, h1), (h2,), (2, h2), (2,))
+    rows = 5 if output in (OUT_CATEGORICAL, OUT_MODE) else 2        # the five logits of Discrete(5), or the two actions
+    want = ((h1, 38), (h1,), (h2, h1), (h2,), (rows, h2), (rows,))
     got = tuple(a.shape for a in (w1, b1, w2, b2, w3, b3))
     if got != want:
-        raise ValueError(f"controller shapes {got}, expected {want} (obs 38 -> h1 -> h2 -> 2 actions)")
-    if activation not in (RELU, TANH) or output not in (OUT_RAW, OUT_CLIP, OUT_SQUASH):
+        raise ValueError(f"controller shapes {got}, expected {want} (obs 38 -> h1 -> h2 -> " +
+                         ("5 logits)" if rows == 5 else "2 actions)"))
+    if activation not in (RELU, TANH) or output not in (OUT_RAW, OUT_CLIP, OUT_SQUASH, OUT_CATEGORICAL, OUT_MODE):
         raise ValueError(f"activation {activation} / output {output} unknown")
     return Controller(w1, b1, w2, b2, w3, b3, h1, h2, int(activation), int(output), kind)
 
@@ -196,9 +202,10 @@ def make_value_net(arrays, activation: int) -> ValueNet:
         raise ValueError(f"value net shapes {got}, expected {want} (obs 38 -> h1 -> h2 -> 1 value)")
     if activation not in (RELU, TANH):
         raise ValueError(f"activation {activation} unknown")
-    if (h1, h2) not in MLP_SHAPES:
+    if (h1, h2) not in MLP_SHAPES and not ((h1, h2) in WIDE_SHAPES and activation == RELU):
         raise ValueError(f"value net shape 38 -> {h1} -> {h2} -> 1 ({'ReLU' if activation == RELU else 'Tanh'}) unsupported: "
-                         f"the kernels hold hidden layers {', '.join('%d-%d' % s for s in MLP_SHAPES)}")
+                         f"the kernels hold hidden layers {', '.join('%d-%d' % s for s in MLP_SHAPES)}, and "
+                         f"{', '.join('%d-%d' % s for s in WIDE_SHAPES)} with ReLU")
     return ValueNet(w1, b1, w2, b2, w3, b3, h1, h2, int(activation))
 
 
@@ -222,6 +229,8 @@ def load_sb3_actor_critic(zip_path: str) -> ActorCritic:
     missing = [k for k in AC_KEYS + VF_KEYS + ("log_std",) if k not in sd]
     if missing:
         what = "an SB3 SAC checkpoint (no value net, no log_std)" if all(k in sd for k in SAC_KEYS) else "no actor-critic"
+        if missing == ["log_std"] and tuple(sd["action_net.weight"].shape)[:1] == (5,):
+            what = "a Discrete(5) policy (no log_std) -- use load_sb3_discrete_actor_critic"
         raise ValueError(f"{zip_path}: {what}: missing {missing[:4]}")
     act = _sb3_activation(zip_path, data)
     return make_actor_critic([sd[k].float().numpy() for k in AC_KEYS], [sd[k].float().numpy() for k in VF_KEYS], act,
@@ -376,3 +385,83 @@ def squashed_actor_numpy(actor: SquashedActor, obs, eps, dtype=np.float64):
     t = np.tanh(mu + np.exp(ls) * np.asarray(eps, dt))
     u = dt(-1) + (dt(0.5) * (t + dt(1))) * dt(2)
     return u, dt(2) * ((u + dt(1)) / dt(2)) - dt(1)
+
+
+# ------------------------------------------------------------------ the categorical actor-critic (policy 6 for Discrete(5))
+N_DISCRETE = 5
+# CarEnv(discrete_action_space=True): action index -> (throttle / brake, steering), BaseEnv._discrete_to_continuous
+DISCRETE_PAIRS = np.array([[0, 0], [1, 0], [-1, 0], [0, -1], [0, 1]], np.float32)
+
+
+class DiscreteActorCritic(NamedTuple):
+    """What SB3's on-policy algorithms train on CarEnv(discrete_action_space=True) (learn/a2c.py): the categorical policy's
+    logit net `pi` (a five-row Controller with OUT_CATEGORICAL) and the critic `vf`; a Discrete(5) policy has no log_std.
+    BatchedCarEnv.set_actor_critic / collect take it like an ActorCritic."""
+    pi: Controller
+    vf: ValueNet
+
+    def deterministic(self) -> Controller:
+        """the arg-max driver (SB3's predict(deterministic=True)): an OUT_MODE Controller for add_controller /
+        set_car_controllers"""
+        return self.pi._replace(output=OUT_MODE)
+
+
+def make_discrete_actor_critic(pi_arrays, vf_arrays, activation: int, kind: str = "random", vf_activation=None) -> DiscreteActorCritic:
+    """A DiscreteActorCritic from the six arrays of each net (PyTorch layouts; the policy head w3 [5, h2], b3 [5])."""
+    return DiscreteActorCritic(make_controller(pi_arrays, activation, OUT_CATEGORICAL, kind),
+                               make_value_net(vf_arrays, activation if vf_activation is None else vf_activation))
+
+
+def load_sb3_discrete_actor_critic(zip_path: str) -> DiscreteActorCritic:
+    """Policy net and value net of an SB3 PPO / A2C checkpoint zip trained on a Discrete(5) action space: the keys of
+    load_sb3_actor_critic without ``log_std``, ``action_net.weight`` [5, h2].  A Box checkpoint (a [2, h2] head) raises
+    ValueError naming load_sb3_actor_critic.  ``policy.pth`` is read with torch.load(weights_only=True): nothing is
+    unpickled; the optimizer is not read."""
+    import torch
+    with zipfile.ZipFile(zip_path) as z:
+        sd = torch.load(io.BytesIO(z.read("policy.pth")), weights_only=True, map_location="cpu")
+        data = json.loads(z.read("data")) if "data" in z.namelist() else {}
+    missing = [k for k in AC_KEYS + VF_KEYS if k not in sd]
+    if missing:
+        what = "an SB3 SAC checkpoint (no value net)" if all(k in sd for k in SAC_KEYS) else "no actor-critic"
+        raise ValueError(f"{zip_path}: {what}: missing {missing[:4]}")
+    head = tuple(sd["action_net.weight"].shape)
+    if len(head) != 2 or head[0] != N_DISCRETE:
+        raise ValueError(f"{zip_path}: action_net.weight is {list(head)}, not [5, h2]: " +
+                         ("a Box(-1, 1)^2 policy -- use load_sb3_actor_critic" if head[:1] == (2,) else
+                          "no Discrete(5) policy"))
+    act = _sb3_activation(zip_path, data)
+    return make_discrete_actor_critic([sd[k].float().numpy() for k in AC_KEYS], [sd[k].float().numpy() for k in VF_KEYS], act,
+                                      "actor_critic")
+
+
+def random_discrete_actor_critic(h1: int, h2: int, activation: int = TANH, seed: int = 0, vf_shape=None,
+                                 vf_activation=None) -> DiscreteActorCritic:
+    """Random-init categorical actor-critic (PyTorch nn.Linear default init): pi 38 -> h1 -> h2 -> 5, vf 38 -> h1 -> h2 -> 1,
+    or `vf_shape` = (h1, h2) / `vf_activation` for a critic of another shape (it then runs in a launch of its own)."""
+    def nets(rng, dims):
+        out = []
+        for shp, fan_in in dims:
+            bound = 1.0 / np.sqrt(fan_in)
+            out.append(rng.uniform(-bound, bound, shp).astype(np.float32))
+        return out
+    pi = nets(np.random.default_rng(seed), (((h1, 38), 38), ((h1,), 38), ((h2, h1), h1), ((h2,), h1),
+                                            ((N_DISCRETE, h2), h2), ((N_DISCRETE,), h2)))
+    v1, v2 = vf_shape or (h1, h2)
+    vf = nets(np.random.default_rng(seed + 7919), (((v1, 38), 38), ((v1,), 38), ((v2, v1), v1), ((v2,), v1), ((1, v2), v2),
+                                                   ((1,), v2)))
+    return make_discrete_actor_critic(pi, vf, activation, "random", vf_activation)
+
+
+def discrete_actor_critic_numpy(ac: DiscreteActorCritic, obs, dtype=np.float64):
+    """Host restatement of the categorical actor-critic's forward in `dtype` arithmetic: (logits [n, 5], value [n])."""
+    dt = np.dtype(dtype).type
+    x = np.asarray(obs, dtype=dt).reshape(-1, 38)
+    out = []
+    for net in (ac.pi, ac.vf):
+        f = (lambda v: np.maximum(v, dt(0))) if net.activation == RELU else np.tanh
+        w1, b1, w2, b2, w3, b3 = [a.astype(dt) for a in net.arrays]
+        h = f(x @ w1.T + b1)
+        h = f(h @ w2.T + b2)
+        out.append(h @ w3.T + b3)
+    return out[0], out[1][:, 0]
