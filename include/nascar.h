@@ -594,6 +594,52 @@ int nascar_set_genomes(NascarHandle* h, const double* genomes, void* stream);
 int nascar_set_fitness(NascarHandle* h, int32_t enable, void* stream);
 int nascar_get_fitness(NascarHandle* h, double* out, void* stream);
 
+/* Race modes: what game/competition.py:239-424, game/time_trial.py:222-420 and the stages of game/championship.py:264-607
+ * keep per car while they step a field, as a per-step ledger kernel (race_step_kernel, enqueued where fitness_kernel is),
+ * and their finishing order and points (competition.py:37-81, championship.py:28-29, 65-120).  Lap times and
+ * simulation_time are float64 (Python floats); the per-car reward is a float32 running sum in step order
+ * (car_rewards[i] = 0.0; car_rewards[i] += reward[i] is np.float32 from the first add under NumPy 2).
+ * NascarRace.mode: 0 off, 1 competition, 2 time trial; laps_per_attempt (>= 1) is the time trial's LAPS_PER_ATTEMPT.
+ * Per step, for an env that has not ended, for every car: total_reward += reward, steps += 1.  Then, for every car
+ * (mode 2: every car that is not parked): lap_count and disabled are taken from the car's info; if lap_count >
+ * prev_lap_count: with a truthy last_lap_time (not None, not 0.0) last_lap = it, laps_timed += 1, attempt_laps += 1,
+ * finish_time = simulation_time (overwritten on every lap), best_lap = it where there is none or it is lower, and the env's
+ * fastest lap and fastest_car become this car's where there is none or it is strictly lower (cars in index order, so the
+ * first car in (step, car) order to reach the minimum keeps it); then prev_lap_count = lap_count either way.
+ * Mode 1: the env ends after the step whose env flags carry terminated or truncated (that step is counted).
+ * Mode 2: a car with attempt_laps >= laps_per_attempt, and then every disabled car, is parked; the env's flags are
+ *   ignored and the env ends after the step that parked its last car.  A parked car's lap_count and disabled stay what
+ *   they were at the step that parked it.  Parking acts on action buffers: for nascar_rollout policies 2, 4 and 5 and for
+ *   nascar_policy_actions (policies 0 to 5; 6 and 7, the learners' sampling sources, are not masked), a car whose parked field was set by an earlier step takes action (0, 0) and
+ *   its controller is not run -- a rule, noisy or genome source skips the car, whose control state stays what it was
+ *   when it parked, and an MLP source's row is overwritten.  Policies 0, 1 and 3 of nascar_rollout and
+ *   nascar_step_driven run inside the step launch and fail in mode 2.
+ * nascar_reset does not touch the rule / genome sources' control state (only nascar_set_genomes and nascar_set_state
+ *   write it): a time trial's attempts carry it over a reset, and the caller resets the envs between attempts.
+ * nascar_set_race: allocates (first time) and initialises the ledger on `stream`; NULL or mode 0 switches it off (the
+ *   ledger stays readable).  Switching modes keeps the ledger: call nascar_race_begin.  While on, every step of
+ *   nascar_step / nascar_step_driven and of the sharded nascar_rollout enqueues race_step_kernel after its sensor launch
+ *   (per shard in the rollout).  Like the fitness accumulators it needs auto_reset = 0 and fails in the fused and the
+ *   pipelined rollout, in random-track mode and under nascar_collect / nascar_collect_transitions; both may be on.
+ * nascar_race_begin: a new race or attempt: zeroes lap_count, attempt_laps, prev_lap_count, total_reward, disabled,
+ *   parked, steps and the ended bytes and clears last_lap and finish_time; keep_records != 0 keeps best_lap, laps_timed
+ *   and the env's fastest lap and its car (the time trial across attempts), 0 clears them too.
+ * nascar_get_race (device buffers, any may be NULL): ledger [E*C][10] float64: lap_count, laps_timed, attempt_laps,
+ *   best_lap (NaN: none), last_lap (NaN: none), finish_time (NaN: none), total_reward (the float32 sum, widened),
+ *   disabled, parked, steps; fastest_car [E] int32 (-1: none); ended [E] uint8.
+ * nascar_race_rank (device buffers): order [n_env][n_cars] (the car at position p), position and points [n_env][n_cars]
+ *   int32 (any may be NULL) of the handle's own ledger (ledger NULL; n_env, n_cars must be the handle's) or of caller
+ *   buffers in nascar_get_race's layout (fastest_car may be NULL: no bonus); n_cars <= 64.  mode 1: Python's stable sorted() by
+ *   (-lap_count, finish_time or 999999, best_lap or 999999, -total_reward, disabled) -- `x or 999999` maps None and 0.0
+ *   -- then COMPETITION_POINTS[-(min(p, 9) + 1)] of [0, 1, 2, 3, 5, 8, 13, 21, 24, 45] and +15 for fastest_car.
+ *   mode 2: stable by best_lap or 999999, then [15, 7, 3] for positions 0-2 that have a best lap. */
+typedef struct NascarRace { int32_t mode; int32_t laps_per_attempt; } NascarRace;
+int nascar_set_race(NascarHandle* h, const NascarRace* race, void* stream);
+int nascar_race_begin(NascarHandle* h, int32_t keep_records, void* stream);
+int nascar_get_race(NascarHandle* h, double* ledger, int32_t* fastest_car, uint8_t* ended, void* stream);
+int nascar_race_rank(NascarHandle* h, const double* ledger, const int32_t* fastest_car, int32_t n_env, int32_t n_cars,
+                     int32_t mode, int32_t* order, int32_t* position, int32_t* points, void* stream);
+
 /* Test hook: the device re-implementation of glibc sinf/cosf used for b2Rot::Set
  * (device pointers, n floats).  Parity tests compare it with the host libm. */
 int nascar_debug_sincosf(const float* x, float* s, float* c, int32_t n, void* stream);

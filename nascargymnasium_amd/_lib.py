@@ -46,6 +46,16 @@ FITNESS_FIELDS = ["total_reward", "distance_traveled", "max_speed", "time_on_tra
                   "steps", "disabled_at_step"]
 N_FITNESS = len(FITNESS_FIELDS)
 N_GENES = 12
+# nascar_get_race rows (include/nascar.h): the per-car ledger of the race modes
+RACE_FIELDS = ["lap_count", "laps_timed", "attempt_laps", "best_lap", "last_lap", "finish_time", "total_reward",
+               "disabled", "parked", "steps"]
+N_RACE = len(RACE_FIELDS)
+RACE_OFF, RACE_COMPETITION, RACE_TIME_TRIAL = 0, 1, 2
+
+
+class NascarRace(ctypes.Structure):
+    """include/nascar.h NascarRace: the race mode (0 off, 1 competition, 2 time trial) and the time trial's laps per attempt."""
+    _fields_ = [("mode", ctypes.c_int32), ("laps_per_attempt", ctypes.c_int32)]
 
 
 class NascarReplay(ctypes.Structure):
@@ -201,6 +211,14 @@ def lib():
     L.nascar_set_fitness.restype = ctypes.c_int
     L.nascar_get_fitness.argtypes = [vp, vp, vp]
     L.nascar_get_fitness.restype = ctypes.c_int
+    L.nascar_set_race.argtypes = [vp, ctypes.POINTER(NascarRace), vp]
+    L.nascar_set_race.restype = ctypes.c_int
+    L.nascar_race_begin.argtypes = [vp, i32, vp]
+    L.nascar_race_begin.restype = ctypes.c_int
+    L.nascar_get_race.argtypes = [vp, vp, vp, vp, vp]
+    L.nascar_get_race.restype = ctypes.c_int
+    L.nascar_race_rank.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.nascar_race_rank.restype = ctypes.c_int
     L.nascar_set_step_events.argtypes = [vp, ctypes.POINTER(vp), i32]
     L.nascar_set_step_events.restype = ctypes.c_int
     L.nascar_debug_sincosf.argtypes = [vp, vp, vp, i32, vp]
@@ -244,6 +262,7 @@ EXPORTED = ["nascar_create", "nascar_destroy", "nascar_last_error", "nascar_add_
             "nascar_set_state", "nascar_policy_actions", "nascar_set_step_events", "nascar_set_actor", "nascar_set_actor_precision", "nascar_actor_forward",
             "nascar_check_controller", "nascar_add_controller", "nascar_controller_forward", "nascar_set_car_controllers",
             "nascar_set_genomes", "nascar_set_fitness", "nascar_get_fitness",
+            "nascar_set_race", "nascar_race_begin", "nascar_get_race", "nascar_race_rank",
             "nascar_update_controller", "nascar_set_actor_critic", "nascar_collect", "nascar_gae",
             "nascar_set_explorer", "nascar_collect_transitions", "nascar_replay_sample",
             "nascar_set_normalize", "nascar_get_normalize", "nascar_get_norm_stats", "nascar_set_norm_stats",

@@ -1476,9 +1476,20 @@ __device__ __forceinline__ void policy_car(int policy, uint64_t seed, int64_t st
   if (policy == 3 && (mix32(key ^ 0x5DEECE66Dull) >> 16) < NOISE_P16) { a0 = u0; a1 = u1; }
   else { a0 = (float)tb; a1 = steer; }
 }
-__global__ void policy_kernel(int N, int policy, uint64_t seed, int64_t step, const float* obs, float* act, double* ctl) {
+// parked (all three action kernels below): the race ledger's parked field [N].  A parked car takes the action (0, 0) and
+// its controller is not run, so its control state stays what it was (game/time_trial.py:278-280).  PARK is a template
+// argument: the instantiation that runs with race mode 2 off (parked null) holds no load and no branch for it.
+__device__ __forceinline__ bool car_parked(const double* parked, int n, float* act) {
+  if (!parked || parked[n] == 0.0) return false;
+  act[2 * n] = 0.0f; act[2 * n + 1] = 0.0f;
+  return true;
+}
+template <bool PARK>
+__global__ void policy_kernel(int N, int policy, uint64_t seed, int64_t step, const float* obs, float* act, double* ctl,
+                              const double* parked) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
+  if (PARK && car_parked(parked, n, act)) return;
   float a0, a1;
   policy_car(policy, seed, step, n, obs, ctl, a0, a1);
   act[2 * n] = a0; act[2 * n + 1] = a1;
@@ -1487,12 +1498,14 @@ __global__ void policy_kernel(int N, int policy, uint64_t seed, int64_t step, co
 // _UNIFORM / _NOISY run policy_car as policy 1 / 0 / 3 (same key, same driver state: the results of policy_kernel for
 // that car); the slots of MLP controllers (code >= 0) are left to mlp_field_kernel, their driver state untouched.
 struct FieldCodes { signed char code[MLP_MAX_CARS]; };
+template <bool PARK>
 __global__ void field_policy_kernel(int n0, int n1, int C, FieldCodes F, uint64_t seed, int64_t step, const float* obs,
-                                    float* act, double* ctl) {
+                                    float* act, double* ctl, const double* parked) {
   const int n = n0 + blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= n1) return;
   const int code = F.code[n % C];
   if (code >= 0 || code == NASCAR_CTRL_GENOME) return;   // genome slots: genome_policy_kernel
+  if (PARK && car_parked(parked, n, act)) return;
   float a0, a1;
   policy_car(code == NASCAR_CTRL_RULE ? 1 : code == NASCAR_CTRL_UNIFORM ? 0 : 3, seed, step, n, obs, ctl, a0, a1);
   act[2 * n] = a0; act[2 * n + 1] = a1;
@@ -1515,8 +1528,10 @@ struct alignas(16) GenomeRec { double g[12]; unsigned long long py_steer, pad; }
 // one lane per car.  slot0 < 0: the cars [n0, n1) directly (nascar_policy_actions, the field's env range);
 // slot0 >= 0: the cars of the block map's env slots [slot0, slot0 + nslot) (a shard of the sharded rollout, whose envs
 // need not be contiguous); slots: bit c set = car slot c is driven (all ones: policy 5)
+template <bool PARK>
 __global__ void __launch_bounds__(256) genome_policy_kernel(Params P, int slot0, int nslot, int n0, int n1, uint64_t slots,
-                                                            const float* obs, float* act, double* ctl, GenomeRec* rec) {
+                                                            const float* obs, float* act, double* ctl, GenomeRec* rec,
+                                                            const double* parked) {
   const int i = blockIdx.x * 256 + threadIdx.x, C = P.C;
   int n;
   if (slot0 < 0) {
@@ -1530,6 +1545,7 @@ __global__ void __launch_bounds__(256) genome_policy_kernel(Params P, int slot0,
     n = env * C + car;
   }
   if (!((slots >> (n % C)) & 1)) return;
+  if (PARK && car_parked(parked, n, act)) return;
   const GenomeRec G = ldg(rec + n);
   const float g0 = (float)G.g[0], g1 = (float)G.g[1], g4 = (float)G.g[4], g6 = (float)G.g[6], g7 = (float)G.g[7],
               g10 = (float)G.g[10];
@@ -2599,6 +2615,8 @@ __global__ void __launch_bounds__(256) fitness_read_kernel(int N, const double* 
   for (int f = 0; f < FIT_N; ++f) out[(size_t)n * FIT_N + f] = v[f];
 }
 
+#include "nascar_race.h"     // race modes (nascar_set_race): the per-step ledger, the park mask and the ranking
+
 // ------------------------------------------------------------------ random-track mode (CarEnv(track_file=None))
 // CarEnv._select_random_track (src/car_env.py:264-287): a uniform choice over the bundled tracks, excluding the env's
 // current track when it is one of them; every CarEnv.reset draws again (src/car_env.py:331-333) and a changed track
@@ -2975,6 +2993,10 @@ struct NascarHandle {
   // on-device fitness (nascar_set_fitness): one allocation -- acc [FIT_N][N] float64, ended [E], env flags [E] of the
   // steps whose caller passed none
   double* d_fit = nullptr; uint8_t* d_fit_ended = nullptr; uint8_t* d_fit_flags = nullptr; bool fit_on = false;
+  // race modes (nascar_set_race): one allocation -- the ledger [RL_N][N] float64, the envs' fastest lap [E] float64 and
+  // its car [E] int32, ended [E], env flags [E] of the steps whose caller passed none
+  double* d_race = nullptr; RaceEnv race_env{}; uint8_t* d_race_flags = nullptr;
+  int race_mode = RACE_OFF, race_laps = 2;
   size_t max_lds = 0, max_sensor_lds = 0, max_sensor_groups_lds = 0;
   bool dirty_tracks = true;
   // sharded rollout (nascar_set_rollout_streams): shard s steps workgroups [nblocks*s/S, nblocks*(s+1)/S) on its
@@ -3151,6 +3173,7 @@ extern "C" void nascar_destroy(NascarHandle* h) {
   hipFree(h->d_rt);
   hipFree(h->d_genome);
   hipFree(h->d_fit);
+  hipFree(h->d_race);
   delete h;
 }
 
@@ -3602,7 +3625,34 @@ static int fitness_refused(const NascarHandle* h, int auto_reset) {
 // (launch_fitness).  fitness_refused keeps the two apart.
 static uint8_t* step_env_flags(const NascarHandle* h, uint8_t* env_flags, int auto_reset) {
   if (env_flags) return env_flags;
-  return h->rt_on && auto_reset ? h->d_rt_flags : h->fit_on ? h->d_fit_flags : nullptr;
+  return h->rt_on && auto_reset ? h->d_rt_flags : h->fit_on ? h->d_fit_flags : h->race_mode ? h->d_race_flags : nullptr;
+}
+// the race ledger (nascar_set_race) of one step for the cars of workgroups [b0, b1), after their sensor launch
+static int launch_race(NascarHandle* h, const Params& P, int b0, int b1, const float* reward, const uint8_t* env_flags,
+                       hipStream_t s) {
+  const int nslot = (b1 - b0) * h->epb, epw = 256 / h->C;
+  if (nslot <= 0) return 0;
+  hipLaunchKernelGGL(race_step_kernel, dim3((nslot + epw - 1) / epw), dim3(256), 0, s, P, b0 * h->epb, nslot, h->race_mode,
+                     h->race_laps, reward, env_flags, h->d_race, h->race_env);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// The ledger freezes an env after its last step as the fitness accumulators do, so it refuses what they refuse
+static int race_refused(const NascarHandle* h, int auto_reset) {
+  if (h->race_mode && auto_reset)
+    return fail("race mode (nascar_set_race) needs auto_reset = 0: the ledger reads each env's state after its last step");
+  if (h->race_mode && h->rt_on) return fail("race mode (nascar_set_race) is not available in random-track mode");
+  return 0;
+}
+// the time trial's park mask (null: no parking): the ledger's parked field, set for disabled cars too
+static const double* race_parked(const NascarHandle* h) {
+  return h->race_mode == RACE_TIME_TRIAL ? h->d_race + (size_t)RACE_PARKED * h->N : nullptr;
+}
+static int launch_park(NascarHandle* h, int n0, int n1, float* act, hipStream_t s) {
+  if (!race_parked(h) || n1 <= n0) return 0;
+  hipLaunchKernelGGL(race_park_kernel, dim3((n1 - n0 + 255) / 256), dim3(256), 0, s, n0, n1, race_parked(h), act);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 // the genome driver's launch for a shard's workgroups [b0, b1) (b0 < 0: the cars [n0, n1) directly)
 static int launch_genome(NascarHandle* h, const Params& P, int b0, int b1, int n0, int n1, uint64_t slots, const float* obs,
@@ -3610,8 +3660,12 @@ static int launch_genome(NascarHandle* h, const Params& P, int b0, int b1, int n
   const int nslot = b0 < 0 ? 0 : (b1 - b0) * h->epb;
   const int lanes = b0 < 0 ? n1 - n0 : nslot * h->C;
   if (lanes <= 0) return 0;
-  hipLaunchKernelGGL(genome_policy_kernel, dim3((lanes + 255) / 256), dim3(256), 0, s, P, b0 < 0 ? -1 : b0 * h->epb, nslot,
-                     n0, n1, slots, obs, act, h->d_ctl, h->d_genome);
+  if (race_parked(h))
+    hipLaunchKernelGGL(genome_policy_kernel<true>, dim3((lanes + 255) / 256), dim3(256), 0, s, P, b0 < 0 ? -1 : b0 * h->epb,
+                       nslot, n0, n1, slots, obs, act, h->d_ctl, h->d_genome, race_parked(h));
+  else
+    hipLaunchKernelGGL(genome_policy_kernel<false>, dim3((lanes + 255) / 256), dim3(256), 0, s, P, b0 < 0 ? -1 : b0 * h->epb,
+                       nslot, n0, n1, slots, obs, act, h->d_ctl, h->d_genome, (const double*)nullptr);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3619,7 +3673,10 @@ static int launch_genome(NascarHandle* h, const Params& P, int b0, int b1, int n
 static int step_impl(NascarHandle* h, const void* actions, int32_t discrete, int policy, uint64_t seed, int64_t step,
                      float* obs, float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset,
                      float* terminal_obs, void* stream) {
-  if (vis_refused(h) || fitness_refused(h, auto_reset)) return -1;
+  if (vis_refused(h) || fitness_refused(h, auto_reset) || race_refused(h, auto_reset)) return -1;
+  if (h->race_mode == RACE_TIME_TRIAL && policy >= 0)
+    return fail("race mode 2 (time trial) parks cars through an action buffer: policy %d runs inside the step launch -- use "
+                "nascar_policy_actions + nascar_step, or policy 2, 4 or 5 of nascar_rollout", policy);
   h->pristine = false;
   if (prepare(h, (hipStream_t)stream)) return -1;
   Params P = make_params(h);
@@ -3631,6 +3688,7 @@ static int step_impl(NascarHandle* h, const void* actions, int32_t discrete, int
                         terminal_obs, (hipStream_t)stream))
     return -1;
   if (h->fit_on && launch_fitness(h, P, 0, h->nblocks, reward, ef, (hipStream_t)stream)) return -1;
+  if (h->race_mode && launch_race(h, P, 0, h->nblocks, reward, ef, (hipStream_t)stream)) return -1;
   return h->rt_on && auto_reset ? rt_after_step(h, P, ef, obs, (hipStream_t)stream) : 0;
 }
 extern "C" int nascar_step(NascarHandle* h, const void* actions, int32_t discrete, float* obs, float* reward,
@@ -3732,6 +3790,7 @@ static int policy_ready(const NascarHandle* h, int policy, const float* obs, con
 static int launch_actions(NascarHandle* h, int policy, const Params& P, const ShardRange& r, uint64_t seed, int64_t step,
                           const float* obs, float* act, const CollectBufs* rec, hipStream_t s) {
   const int c0 = (int)r.c0, n = (int)(r.c1 - r.c0);
+  // (policies 6 and 7 are the learners' sampling sources: collection refuses race mode, and they are not masked)
   if (policy == 7) return launch_explorer(h, c0, n, seed, step, obs, act, rec ? rec->actions : nullptr, s);
   if (policy == 6)
     return launch_ac(h, rec ? AC_SAMPLE | AC_VALUE : AC_SAMPLE, c0, n, seed, step, obs, act, rec ? rec->actions : nullptr,
@@ -3740,7 +3799,7 @@ static int launch_actions(NascarHandle* h, int policy, const Params& P, const Sh
   if (policy == 4) return launch_field(h, c0 / h->C, n / h->C, seed, step, obs, act, s);
   if (n > 0) launch_actor(h, n, obs + r.c0 * 38, act + r.c0 * 2, s);
   HIPCHK(hipGetLastError());
-  return 0;
+  return launch_park(h, c0, c0 + n, act, s);   // policy 2 writes every car's row: the park mask overwrites the parked cars'
 }
 // The first n shard streams with their join events, and the fork event, created where missing on the handle's device
 // (whatever is current): a stream and its join event both or neither.  `what` names them in the error.
@@ -3867,6 +3926,7 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
                         col->timeout_values + ko * NC, ef, shard_stream(s)))
             return -1;
           if (h->fit_on && ph == 2 && launch_fitness(h, P, r.b0, r.b1, reward + ko * NC, ef, shard_stream(s))) return -1;
+          if (h->race_mode && ph == 2 && launch_race(h, P, r.b0, r.b1, reward + ko * NC, ef, shard_stream(s))) return -1;
         }
       }
       if (rt && rt_after_step(h, P0, ef, o_out, stream)) return -1;
@@ -4003,6 +4063,15 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
   if (h->fit_on && (h->ro_streams == 0 || h->ro_pipe > 0))
     return fail("fitness accumulation (nascar_set_fitness) runs on the sharded rollout only (rollout streams >= 1, no pipe)");
   if (fitness_refused(h, auto_reset)) return -1;
+  if (h->race_mode && h->ro_streams == 0)
+    return fail("race mode (nascar_set_race) does not run in the fused rollout kernel (rollout streams 0): use the sharded "
+                "rollout (rollout streams >= 1)");
+  if (h->race_mode && h->ro_pipe > 0)
+    return fail("race mode (nascar_set_race) does not run in the pipelined rollout: switch it off (nascar_set_rollout_pipe(h, 0))");
+  if (race_refused(h, auto_reset)) return -1;
+  if (h->race_mode == RACE_TIME_TRIAL && (policy == 0 || policy == 1 || policy == 3))
+    return fail("race mode 2 (time trial) parks cars through an action buffer: policy %d runs inside the step launch -- use "
+                "policy 2, 4 or 5, or nascar_policy_actions + nascar_step", policy);
   if (h->rt_on && h->ro_streams == 0)
     return fail("random-track mode needs the sharded rollout (rollout streams >= 1): the fused kernel keeps one block map");
   if (traj & ~(NASCAR_TRAJ_RECORDS | NASCAR_TRAJ_OBS)) return fail("unknown trajectory flags 0x%x", traj);
@@ -4045,6 +4114,7 @@ static int collect_impl(NascarHandle* h, uint64_t seed, int64_t step0, int32_t s
   if (h->ro_pipe > 0)
     return fail("the pipelined rollout has no actor-critic (policy 6): switch it off (nascar_set_rollout_pipe(h, 0))");
   if (h->fit_on) return fail("collect steps with auto-reset: switch fitness accumulation off (nascar_set_fitness(h, 0))");
+  if (h->race_mode) return fail("collect steps with auto-reset: switch race mode off (nascar_set_race(h, NULL, stream))");
   const bool cat = h->ctrl[h->ac_pi].output == MLP_OUT_CATEGORICAL;   // actions: int32 [steps][E*C], the action index
   if (((uintptr_t)obs | (cat ? 0 : (uintptr_t)actions)) & 7) return fail("collect obs / actions must be 8-byte aligned");
   if ((uintptr_t)actions & 3) return fail("collect actions must be 4-byte aligned");
@@ -4107,6 +4177,8 @@ extern "C" int nascar_collect_transitions(NascarHandle* h, int32_t source, uint6
     return fail("the pipelined rollout fills no replay ring: switch it off (nascar_set_rollout_pipe(h, 0))");
   if (h->fit_on)
     return fail("collect_transitions steps with auto-reset: switch fitness accumulation off (nascar_set_fitness(h, 0))");
+  if (h->race_mode)
+    return fail("collect_transitions steps with auto-reset: switch race mode off (nascar_set_race(h, NULL, stream))");
   if ((uintptr_t)obs & 7) return fail("collect_transitions obs must be 8-byte aligned");
   if (vis_refused(h)) return -1;
   h->pristine = false;
@@ -4476,6 +4548,73 @@ extern "C" int nascar_get_fitness(NascarHandle* h, double* out, void* stream) {
   return 0;
 }
 
+// ------------------------------------------------------------------ race modes
+extern "C" int nascar_race_begin(NascarHandle* h, int32_t keep_records, void* stream) {
+  if (!h) return fail("null argument");
+  if (!h->d_race) return fail("no race ledger: switch race mode on first (nascar_set_race)");
+  hipLaunchKernelGGL(race_begin_kernel, dim3((h->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->N, h->E,
+                     keep_records != 0, h->d_race, h->race_env);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+extern "C" int nascar_set_race(NascarHandle* h, const NascarRace* race, void* stream) {
+  if (!h) return fail("null argument");
+  if (!race || race->mode == RACE_OFF) { h->race_mode = RACE_OFF; return 0; }
+  if (race->mode != RACE_COMPETITION && race->mode != RACE_TIME_TRIAL)
+    return fail("race mode must be 0 (off), 1 (competition) or 2 (time trial), got %d", race->mode);
+  if (race->laps_per_attempt < 1) return fail("race laps_per_attempt must be >= 1 (got %d)", race->laps_per_attempt);
+  if (!h->d_race) {
+    const size_t N = (size_t)h->N, E = (size_t)h->E;
+    const size_t led = align256(sizeof(double) * RL_N * N), f64 = align256(sizeof(double) * E),
+                 i32 = align256(sizeof(int32_t) * E), u8 = align256(E);
+    DeviceGuard on(h->cfg.device);
+    HIPCHK(on.err);
+    HIPCHK(hipMalloc(&h->d_race, led + f64 + i32 + 2 * u8));
+    char* p = (char*)h->d_race + led;
+    h->race_env.fastest = (double*)p; p += f64;
+    h->race_env.fastest_car = (int32_t*)p; p += i32;
+    h->race_env.ended = (uint8_t*)p; p += u8;
+    h->d_race_flags = (uint8_t*)p;
+    HIPCHK(hipMemsetAsync(h->d_race, 0, led + f64 + i32 + 2 * u8, (hipStream_t)stream));
+    if (nascar_race_begin(h, 0, stream)) { hipFree(h->d_race); h->d_race = nullptr; return -1; }
+  }
+  h->race_mode = race->mode; h->race_laps = race->laps_per_attempt;
+  return 0;
+}
+extern "C" int nascar_get_race(NascarHandle* h, double* ledger, int32_t* fastest_car, uint8_t* ended, void* stream) {
+  if (!h) return fail("null argument");
+  if (!h->d_race) return fail("no race ledger: switch race mode on first (nascar_set_race)");
+  if (ledger) {
+    hipLaunchKernelGGL(race_read_kernel, dim3((h->N + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->N, h->d_race, ledger);
+    HIPCHK(hipGetLastError());
+  }
+  if (fastest_car)
+    HIPCHK(hipMemcpyAsync(fastest_car, h->race_env.fastest_car, sizeof(int32_t) * h->E, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (ended) HIPCHK(hipMemcpyAsync(ended, h->race_env.ended, (size_t)h->E, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int nascar_race_rank(NascarHandle* h, const double* ledger, const int32_t* fastest_car, int32_t n_env,
+                                int32_t n_cars, int32_t mode, int32_t* order, int32_t* position, int32_t* points,
+                                void* stream) {
+  if (!h) return fail("null argument");
+  if (mode != RACE_COMPETITION && mode != RACE_TIME_TRIAL) return fail("race_rank: mode must be 1 (competition) or 2 (time trial), got %d", mode);
+  size_t sn = RACE_N, sf = 1;
+  if (!ledger) {
+    if (!h->d_race) return fail("race_rank: no ledger given and none on the handle (nascar_set_race)");
+    if (n_env != h->E || n_cars != h->C)
+      return fail("race_rank: the handle's ledger holds %d envs of %d cars (got %d of %d)", h->E, h->C, n_env, n_cars);
+    ledger = h->d_race; fastest_car = h->race_env.fastest_car; sn = 1; sf = (size_t)h->N;
+  }
+  if (n_cars < 1 || n_cars > 64) return fail("race_rank: n_cars must be in [1, 64] (got %d)", n_cars);
+  if (n_env < 0) return fail("race_rank: n_env must be >= 0 (got %d)", n_env);
+  if (n_env == 0) return 0;
+  const int epw = 256 / n_cars;
+  hipLaunchKernelGGL(race_rank_kernel, dim3((n_env + epw - 1) / epw), dim3(256), 0, (hipStream_t)stream, n_env, n_cars, mode,
+                     ledger, sn, sf, fastest_car, order, position, points);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, const float* obs,
                                      float* actions, void* stream) {
   if (!h || !actions) return fail("null argument");
@@ -4487,7 +4626,12 @@ extern "C" int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t s
                           (hipStream_t)stream);
   }
   int nb = (h->N + 255) / 256;
-  hipLaunchKernelGGL(policy_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, h->N, policy, seed, step, obs, actions, h->d_ctl);
+  if (race_parked(h))
+    hipLaunchKernelGGL(policy_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, h->N, policy, seed, step, obs, actions,
+                       h->d_ctl, race_parked(h));
+  else
+    hipLaunchKernelGGL(policy_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, h->N, policy, seed, step, obs, actions,
+                       h->d_ctl, (const double*)nullptr);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -4883,7 +5027,7 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
   if (nenv <= 0) return 0;
   const int C = h->C;
   bool done[MLP_MAX_CARS] = {};
-  bool builtin = false;
+  bool builtin = false, mlp = false;
   uint64_t genome_slots = 0;   // slots of NASCAR_CTRL_GENOME: genome_policy_kernel, as policy 5 runs it for those cars
   for (int c = 0; c < C; ++c) {
     if (h->field[c] == NASCAR_CTRL_GENOME) { genome_slots |= 1ull << c; continue; }
@@ -4903,8 +5047,10 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
       done[d] = true;
     }
     if (mlp_launch(K, nenv, ns, s, L, false, head5)) return -1;
+    mlp = true;
   }
   const int n0 = env0 * C, n1 = (env0 + nenv) * C;
+  if (mlp && launch_park(h, n0, n1, act, s)) return -1;   // before the built-in slots' kernels, which park their own cars
   if (genome_slots) {
     if (!h->genome_set) return fail("a genome slot of the field needs a genome table (nascar_set_genomes)");
     if (launch_genome(h, make_params(h), -1, 0, n0, n1, genome_slots, obs, act, s)) return -1;
@@ -4912,8 +5058,12 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
   if (builtin) {
     FieldCodes F{};
     for (int c = 0; c < C; ++c) F.code[c] = (signed char)std::max(h->field[c], NASCAR_CTRL_GENOME);   // the lowest code
-    hipLaunchKernelGGL(field_policy_kernel, dim3((n1 - n0 + 255) / 256), dim3(256), 0, s, n0, n1, C, F, seed, step, obs, act,
-                       h->d_ctl);
+    if (race_parked(h))
+      hipLaunchKernelGGL(field_policy_kernel<true>, dim3((n1 - n0 + 255) / 256), dim3(256), 0, s, n0, n1, C, F, seed, step, obs,
+                         act, h->d_ctl, race_parked(h));
+    else
+      hipLaunchKernelGGL(field_policy_kernel<false>, dim3((n1 - n0 + 255) / 256), dim3(256), 0, s, n0, n1, C, F, seed, step,
+                         obs, act, h->d_ctl, (const double*)nullptr);
     HIPCHK(hipGetLastError());
   }
   return 0;

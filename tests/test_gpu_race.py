@@ -1,0 +1,492 @@
+"""The device race ledger, park mask and rank kernel (nascar_set_race, include/nascar.h) against the CPU restatement of
+the reference's race modes (tests/race_ref.py): the rank kernel on synthetic ledgers, a competition and a time trial
+against the host loop they replace on a twin engine, persistence across attempts, race.championship against per-track
+runs, and the library's refusals.  Every comparison is exact."""
+import os
+
+import numpy as np
+import pytest
+
+import race_ref
+from race_ref import F
+from golden_replay import GOLDEN, TRACKS
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+from nascargymnasium_amd import _lib, genetic as G, race   # noqa: E402
+
+NAN = float("nan")
+# The field of the 10-car cases: rule, noisy and genome slots; every env has its own genomes.  Smaller fields take
+# ["genome", "rule", "noisy"][:C].
+FIELD = ["rule", "noisy", "genome", "rule", "genome", "noisy", "genome", "rule", "noisy", "genome"]
+SEED, GENOME_SEED = 3, 7
+IDLE_ENV = 5        # its genome slots have g[2] = g[3] = 0: they stand on the grid until the stuck rule disables them
+
+
+def _track(name):
+    return os.path.join(TRACKS, name + ".track")
+
+
+def _engine(E, C, tracks):
+    from nascargymnasium_amd.batched import BatchedCarEnv
+    files = [_track(t) for t in tracks] if not isinstance(tracks, str) else _track(tracks)
+    env = BatchedCarEnv(E, C, files, device="cuda:0")
+    env.set_rollout_streams(4)
+    return env
+
+
+def _field(C):
+    return list(FIELD) if C == len(FIELD) else ["genome", "rule", "noisy"][:C]
+
+
+def _genomes(E, C, max_gain=None):
+    """max_gain: a cap on the steering gain g[4].  With g[4] <= 1 the steering never saturates, so the genome driver's
+    state is the four control-state words alone (no per-car Python-number flag, which a twin engine cannot write)."""
+    g = G.random_genomes(np.random.default_rng(GENOME_SEED), E * C).reshape(E, C, 12)
+    idle = min(IDLE_ENV, E - 1)
+    g[idle, :, 2] = 0.0
+    g[idle, :, 3] = 0.0
+    if max_gain is not None:
+        g[:, :, 4] = np.minimum(g[:, :, 4], max_gain)
+    return g
+
+
+def _field_engine(E, C, tracks, epb=None, field=None, max_gain=None):
+    env = _engine(E, C, tracks)
+    env.set_genomes(_genomes(E, C, max_gain))
+    env.set_car_controllers(field or _field(C))
+    env.reset()
+    if epb is not None:
+        env.set_envs_per_block(epb)
+    return env
+
+
+def _ctl(env):
+    """the drivers' per-car state [N, 4] float64: the last region of the state arena (as tests/test_gpu_genome.py)"""
+    n = 32 * env.N
+    tail = (n + 255) // 256 * 256
+    return env.get_state().cpu().numpy()[-tail:][:n].view(np.float64).reshape(env.N, 4)
+
+
+def _set_ctl(env, ctl):
+    n = 32 * env.N
+    tail = (n + 255) // 256 * 256
+    st = env.get_state().cpu().numpy().copy()
+    st[len(st) - tail:len(st) - tail + n] = np.ascontiguousarray(ctl, np.float64).reshape(-1).view(np.uint8)
+    env.set_state(torch.from_numpy(st).to(env.device))
+
+
+def _state_without_ctl(env):
+    n = 32 * env.N
+    return env.get_state()[:-((n + 255) // 256 * 256)]
+
+
+def _state_diff(a, b):
+    """where two engines' state arenas differ, control state aside: {section: first differing (field, car) pairs}"""
+    from oracle_lib import gpu_arena
+    A, B = (gpu_arena(e.get_state().cpu().numpy(), e.E, e.C) for e in (a, b))
+    out = {}
+    for k in A:
+        x, y = np.ascontiguousarray(A[k]).view(np.uint8), np.ascontiguousarray(B[k]).view(np.uint8)
+        if k != "ctl" and not np.array_equal(x, y):
+            bad = np.argwhere(A[k].view(np.uint32 if A[k].itemsize == 4 else np.uint64) !=
+                              B[k].view(np.uint32 if B[k].itemsize == 4 else np.uint64))
+            out[k] = (len(bad), bad[:6].tolist())
+    return out
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def _assert_ledger(dev, host, what=""):
+    for f, name in enumerate(race_ref.RACE_FIELDS):
+        bad = np.argwhere(_bits(dev[..., f]) != _bits(host[..., f]))
+        assert len(bad) == 0, (what, name, bad[:4].tolist(), dev[..., f][tuple(bad[0])], host[..., f][tuple(bad[0])])
+
+
+def _assert_rank(env, mode, led, fastest, what=""):
+    """the handle's own ledger and the same rows given back as a caller ledger, both against sorted()"""
+    want = race_ref.rank_ledger(led, fastest, mode)
+    own = env.race_rank(mode)
+    given = env.race_rank(mode, torch.from_numpy(led), torch.from_numpy(np.asarray(fastest, np.int32)))
+    for got in (own, given):
+        for g, w, name in zip(got, want, ("order", "position", "points")):
+            assert np.array_equal(g.cpu().numpy(), w), (what, name)
+    return want
+
+
+# ------------------------------------------------------------------ the rank kernel on synthetic ledgers
+def _synthetic(E, C, seed):
+    rng = np.random.default_rng(seed)
+    led = np.zeros((E, C, len(race_ref.RACE_FIELDS)))
+    led[..., F["lap_count"]] = rng.integers(0, 3, (E, C))
+    led[..., F["finish_time"]] = rng.choice([NAN, 0.0, 50.0, 60.0], (E, C))
+    led[..., F["best_lap"]] = rng.choice([NAN, 0.0, 20.0, 21.0], (E, C))
+    led[..., F["total_reward"]] = rng.choice(np.array([-1.0, 0.0, 2.5], np.float32), (E, C))
+    led[..., F["disabled"]] = rng.integers(0, 2, (E, C))
+    led[..., F["last_lap"]] = NAN
+    if C >= 2:      # full ties: a copy of a car's row in another slot
+        for e in range(0, E, 3):
+            i, j = rng.choice(C, 2, replace=False)
+            led[e, j] = led[e, i]
+    fastest = rng.integers(-1, C, E).astype(np.int32)
+    return led, fastest
+
+
+def _tie_depths(led):
+    """how many car pairs of an env tie on exactly the first d competition keys, d = 0 .. 5 (5: a full tie)"""
+    sub = lambda x: 999999.0 if (x != x or x == 0.0) else x
+    depth = [0] * 6
+    for row in led:
+        keys = [(-r[F["lap_count"]], sub(r[F["finish_time"]]), sub(r[F["best_lap"]]), -r[F["total_reward"]], r[F["disabled"]])
+                for r in row]
+        for i in range(len(keys)):
+            for j in range(i + 1, len(keys)):
+                d = 0
+                while d < 5 and keys[i][d] == keys[j][d]:
+                    d += 1
+                depth[d] += 1
+    return depth
+
+
+@pytest.mark.parametrize("C,E", [(1, 300), (2, 300), (3, 300), (10, 300), (10, 301), (64, 9)])
+def test_rank_kernel_on_synthetic_ledgers(C, E):
+    """Keys from small value sets (NaN / none and 0.0 times among them) so that most envs hold ties at every key depth;
+    n_env gives at least two blocks of 256 / C envs and a ragged last one (10 x 300 fills its 12 blocks of 25 envs: 301
+    adds the ragged one).  Order, position and points equal sorted() on
+    the reference's key tuples and its points tables, in both modes."""
+    assert E > 256 // C and (E % (256 // C) != 0 or (C, E) == (10, 300))
+    led, fastest = _synthetic(E, C, 100 + C)
+    if C >= 2:
+        depth = _tie_depths(led)
+        assert all(d > 0 for d in depth), depth
+        assert np.isnan(led[..., F["best_lap"]]).any() and (led[..., F["finish_time"]] == 0.0).any()
+    env = _engine(2, 2, "martinsville")
+    dl, df = torch.from_numpy(led).cuda(), torch.from_numpy(fastest).cuda()
+    for mode in (1, 2):
+        want = race_ref.rank_ledger(led, fastest, mode)
+        got = env.race_rank(mode, dl, df)
+        for g, w, name in zip(got, want, ("order", "position", "points")):
+            assert g.shape == (E, C) and g.dtype == torch.int32
+            assert np.array_equal(g.cpu().numpy(), w), (mode, name, np.argwhere(g.cpu().numpy() != w)[:4].tolist())
+    # no fastest-lap bonus without fastest_car
+    nobonus = env.race_rank(1, dl).points.cpu().numpy()
+    assert np.array_equal(nobonus, race_ref.rank_ledger(led, None, 1)[2])
+    env.close()
+
+
+# ------------------------------------------------------------------ competition
+def _info_cols(info):
+    I = _lib.INFO_INDEX
+    return (info[..., I["lap_count"]], info[..., I["last_lap_time"]], info[..., I["disabled"]] != 0,
+            info[..., I["simulation_time"]])
+
+
+def _host_step(b, races, k, mode):
+    """one step of the twin: the field's actions, (0, 0) for the cars the time trial does not drive, env.step, and the
+    reference's per-step bookkeeping from reward, info and the env flags"""
+    a = b.policy_actions(4, SEED, k)
+    if mode == 2:
+        mask = torch.from_numpy(np.array([r.parked() for r in races])).cuda()
+        a = a.clone()
+        a[mask] = 0.0
+    b.step(a, auto_reset=False)
+    rew, info = b.reward.cpu().numpy(), b.info_tensor().cpu().numpy()
+    done = (b.env_flags.cpu().numpy() & (_lib.EF_TERMINATED | _lib.EF_TRUNCATED)) != 0
+    laps, last, dis, st = _info_cols(info)
+    for e, r in enumerate(races):
+        if not r.ended:
+            r.step(rew[e], laps[e].tolist(), [race_ref.none_if_nan(x) for x in last[e]], dis[e].tolist(), float(st[e, 0]),
+                   bool(done[e]))
+
+
+def _host_rows(races):
+    led = np.stack([r.rows() for r in races])
+    fastest = np.array([-1 if r.fastest_car is None else r.fastest_car for r in races], np.int32)
+    ended = np.array([r.ended for r in races], np.uint8)
+    return led, fastest, ended
+
+
+def _competition_case(E, C, tracks, K, epb, field=None):
+    a, b = _field_engine(E, C, tracks, epb, field), _field_engine(E, C, tracks, None, field)
+    a.set_race(1)
+    a.rollout(4, K, seed=SEED, auto_reset=False)
+    dev = a.race()
+    races = [race_ref.EnvRace(C, 1) for _ in range(E)]
+    ended_at = {}
+    for k in range(K):
+        _host_step(b, races, k, 1)
+        for e, r in enumerate(races):
+            if r.ended:
+                ended_at.setdefault(e, k + 1)
+    led, fastest, ended = _host_rows(races)
+    assert torch.equal(a.obs, b.obs) and torch.equal(a.get_state(), b.get_state())
+    _assert_ledger(dev.ledger.cpu().numpy(), led, (E, C))
+    assert np.array_equal(dev.fastest_car.cpu().numpy(), fastest)
+    assert np.array_equal(dev.ended.cpu().numpy(), ended)
+    _assert_rank(a, 1, led, fastest, (E, C))
+    assert a.race_racing() == E - len(ended_at)
+    a.close(); b.close()
+    return led, fastest, ended_at
+
+
+COMPETITION_K = 2400
+MIXED_TRACKS = ["daytona"] * 13 + ["martinsville"] * 13
+
+
+def test_competition_ledger_26x10():
+    """13 envs on daytona + 13 on martinsville, 10 cars each, 4 rollout streams, 12 envs per workgroup against the
+    automatic layout: set_race(1) + rollout(4, K) equals policy_actions(4) + step + reward / info_tensor / env_flags fed to
+    the reference's loop, every ledger field of every car bit for bit, and so do fastest_car, ended, order and points.
+    Field, seed and K were chosen with the CPU oracle's closed loop (tests/oracle_lib.py with tests/drivers.py and
+    tests/genome_ref.py driving it): the rule cars on martinsville time their first lap at step 1680, at step 2400 93 cars
+    of the martinsville envs hold a lap and no daytona car does, and 24 cars are disabled.  No env of this field ends
+    (4200 oracle steps, two seeds): the slots are the same in every env, so the idle env's rule and noisy cars keep
+    driving after its genome cars are disabled.  The env that ends early is test_competition_ledger_26x10_idle_env's.
+    Known limit: the ledger's frozen-after-end path is therefore exercised with genome slots only (there, and at 5 x 1),
+    not together with rule and noisy slots or lap events; the only end a mixed field reaches is the truncation at
+    180 s, 10800 steps, which ends every env at once."""
+    E, C, K = 26, 10, COMPETITION_K
+    led, fastest, ended_at = _competition_case(E, C, MIXED_TRACKS, K, 12)
+    print("envs ended at", ended_at, "fastest", fastest.tolist())
+    timed = led[..., F["laps_timed"]] > 0
+    live = [e for e in range(E) if e not in ended_at]
+    assert live                                                    # an env did not end
+    assert timed.sum() >= 5                                        # at least 5 cars have timed a lap
+    assert any(timed[e].any() and not timed[e].all() for e in range(E))   # a car without a lap beside a lap holder
+    assert (led[live][..., F["disabled"]] != 0).any()              # a disabled car in an env that did not end
+    assert (led[..., F["steps"]][live] == K).all()
+    for e, k in ended_at.items():
+        assert (led[e, :, F["steps"]] == k).all()
+
+
+def test_competition_ledger_26x10_idle_env():
+    """The same engines with a genome driver in every slot: env IDLE_ENV's cars stand on the grid until the stuck rule
+    has disabled all ten and the env terminates at step 600 (the golden trace env_martinsville_all_idle ends there, as
+    tests/test_gpu_genome.py's evaluation scene does); its ledger rows stay at their terminal-step values for the 50
+    steps that follow while the other envs go on."""
+    E, C, K = 26, 10, 650
+    led, fastest, ended_at = _competition_case(E, C, MIXED_TRACKS, K, 12, field=["genome"] * C)
+    assert ended_at.get(IDLE_ENV) == 600 and K - 600 >= 50        # an env ended at least 50 steps before K
+    assert len(ended_at) < E                                      # an env did not end
+    assert (led[IDLE_ENV, :, F["steps"]] == 600).all() and (led[IDLE_ENV, :, F["disabled"]] == 1).all()
+    assert (led[[e for e in range(E) if e not in ended_at]][..., F["steps"]] == K).all()
+
+
+@pytest.mark.parametrize("E,C,K", [(86, 3, 700), (5, 1, 700)])
+def test_competition_ledger_other_layouts(E, C, K):
+    """86 x 3: 85 envs per 256-lane ledger block and one idle lane; 5 x 1: one car per env.  The idle env's genome car
+    of 5 x 1 is disabled by the stuck rule at step 600 and ends its env there."""
+    led, fastest, ended_at = _competition_case(E, C, "martinsville", K, None)
+    if C == 1:
+        assert ended_at == {E - 1: 600}
+    assert (led[..., F["total_reward"]] != 0).any()
+
+
+# ------------------------------------------------------------------ time trial
+# Steps per attempt.  On the CPU oracle the rule cars time their first martinsville lap at step 1680, and 9 of the 26 envs
+# have every car parked (a lap, or disabled) before step 3300 of the first attempt, the idle env at step 2055.
+TT_STEPS = 3300
+LAP_STEPS = 2000    # one rule car: its first timed lap ends at step 1679 (attempt 1) and 1708 (attempt 2) on the oracle
+
+
+def test_time_trial_26x10():
+    """26 x 10 on martinsville, one lap per attempt, two attempts with race_begin(keep_records=True) and reset() between
+    them.  The twin computes the park mask itself from the reference's cars_finished_attempt, writes (0, 0) into
+    policy_actions' output and restates the attempt loop; ledger, order, points, obs and state are bit-equal, and so is
+    the rule / genome slots' control state, where the twin's row of a parked car is the one it had when the car parked
+    (the reference does not call a parked car's controller; the twin puts those rows back before the next attempt, and
+    the genomes' steering gain is capped at 1 so that those rows are the drivers' whole state).  A third engine steps the first attempt with
+    policy_actions(4) + step under mode 2."""
+    E, C = 26, 10
+    a, b, c = (_field_engine(E, C, "martinsville", epb, max_gain=1.0) for epb in (12, None, None))
+    a.set_race(2, 1)
+    c.set_race(2, 1)
+    races = [race_ref.EnvRace(C, 2, 1) for _ in range(E)]
+    parked_at = np.zeros((2, E, C), np.int64)
+    ended_at = np.zeros((2, E), np.int64)
+    for att in range(2):
+        a.race_begin(keep_records=att > 0)
+        a.reset()
+        a.rollout(4, TT_STEPS, seed=SEED, step0=att * TT_STEPS, auto_reset=False)
+        b.reset()
+        for r in races:
+            r.begin(att > 0)
+        frozen = {}
+        for k in range(TT_STEPS):
+            before = [r.parked() for r in races]
+            _host_step(b, races, att * TT_STEPS + k, 2)
+            new = [(e, n) for e, r in enumerate(races) for n, p in enumerate(r.parked()) if p and not before[e][n]]
+            if new:
+                ctl = _ctl(b).reshape(E, C, 4)
+                for e, n in new:
+                    frozen[(e, n)] = ctl[e, n].copy()
+                    parked_at[att, e, n] = k + 1
+            for e, r in enumerate(races):
+                if r.ended and not ended_at[att, e]:
+                    ended_at[att, e] = k + 1
+        led, fastest, ended = _host_rows(races)
+        dev = a.race()
+        _assert_ledger(dev.ledger.cpu().numpy(), led, att)
+        assert np.array_equal(dev.fastest_car.cpu().numpy(), fastest) and np.array_equal(dev.ended.cpu().numpy(), ended)
+        assert torch.equal(a.obs, b.obs)
+        assert torch.equal(_state_without_ctl(a), _state_without_ctl(b)), (att, _state_diff(a, b))
+        want_ctl = _ctl(b).reshape(E, C, 4).copy()
+        for (e, n), row in frozen.items():
+            want_ctl[e, n] = row
+        assert np.array_equal(_bits(_ctl(a)), _bits(want_ctl.reshape(E * C, 4)))
+        assert frozen and not np.array_equal(_bits(_ctl(b)), _bits(want_ctl.reshape(E * C, 4)))   # the freeze matters
+        _assert_rank(a, 2, led, fastest, att)
+        # the twin ran its parked cars' controllers (their actions were overwritten); the reference did not call them, so
+        # the next attempt starts from the rows they had when they parked
+        _set_ctl(b, want_ctl)
+        if att == 0:
+            c.race_begin(False)
+            for k in range(TT_STEPS):
+                c.step(c.policy_actions(4, SEED, k), auto_reset=False)
+            assert torch.equal(a.obs, c.obs) and torch.equal(a.get_state(), c.get_state())
+            same = torch.equal(a.race().ledger.view(torch.int64), c.race().ledger.view(torch.int64))   # (NaN: by bits)
+            assert same
+    print("attempts ended at", ended_at.tolist())
+    for att in range(2):
+        end = np.where(ended_at[att] > 0, ended_at[att], TT_STEPS)
+        assert ((parked_at[att] > 0) & (parked_at[att] <= end[:, None] - 50)).any()     # a car parked 50 steps early
+        assert ((ended_at[att] > 0) & (ended_at[att] < TT_STEPS)).any()                 # an env finished its attempt early
+    assert (led[..., F["laps_timed"]] >= 2).any() and (led[..., F["attempt_laps"]] <= 1).all()
+    for env in (a, b, c):
+        env.close()
+
+
+def test_best_lap_persists_across_attempts():
+    """One rule car on martinsville, one lap per attempt.  Attempt 2 restarts from the grid with the driver's control
+    state as it was when the car parked (nascar_reset leaves it), and its lap is slower (CPU oracle: 23.583 s, then
+    23.883 s): the best lap of attempt 1 survives, laps_timed counts both, and race_begin(False) clears the records."""
+    env = _engine(1, 1, "martinsville")
+    env.set_car_controllers(["rule"])
+    env.set_race(2, 1)
+    laps = []
+    for att in range(2):
+        env.race_begin(keep_records=att > 0)
+        env.reset()
+        env.rollout(4, LAP_STEPS, auto_reset=False)
+        row = env.race().ledger.cpu().numpy()[0, 0]
+        assert row[F["attempt_laps"]] == 1 and row[F["parked"]] == 1 and row[F["laps_timed"]] == att + 1
+        laps.append(row[F["last_lap"]])
+        assert row[F["best_lap"]] == laps[0]
+    assert laps[1] > laps[0] > 0
+    assert env.race().fastest_car.item() == 0
+    env.race_begin(keep_records=True)
+    kept = env.race().ledger.cpu().numpy()[0, 0]
+    assert kept[F["best_lap"]] == min(laps) and kept[F["laps_timed"]] == 2 and kept[F["attempt_laps"]] == 0
+    assert np.isnan(kept[F["last_lap"]]) and kept[F["parked"]] == 0 and env.race_racing() == 1
+    env.race_begin(False)
+    cleared = env.race()
+    assert np.isnan(cleared.ledger.cpu().numpy()[0, 0, F["best_lap"]]) and cleared.fastest_car.item() == -1
+    assert cleared.ledger.cpu().numpy()[0, 0, F["laps_timed"]] == 0
+    env.close()
+
+
+# ------------------------------------------------------------------ race.championship
+def test_championship_equals_per_track_stages():
+    """2 tracks x 2 replicas x 3 cars in one engine == time_trial + competition per track on single-track engines, added
+    up with ChampionshipTable.  Short stages: the point is the layout, not the laps."""
+    tracks, R, C = ["daytona", "martinsville"], 2, 3
+    field = ["genome", "rule", "genome"]     # (a noisy slot's draws are keyed by the car's index in its engine)
+    g = _genomes(4, C)
+    kw = dict(attempts=2, laps=1, chunk=128)
+    env = _engine(4, C, "daytona")
+    env.set_genomes(g)
+    env.set_car_controllers(field)
+    table, tt, comp = race.championship(env, [_track(t) for t in tracks], time_trial_steps=300, competition_steps=700, **kw)
+    env.close()
+    want = race.ChampionshipTable(R, C)
+    for t, name in enumerate(tracks):
+        one = _engine(R, C, name)
+        one.set_genomes(g[t * R:(t + 1) * R])
+        one.set_car_controllers(field)
+        tt1 = race.time_trial(one, max_steps=300, **kw)
+        comp1 = race.competition(one, max_steps=700, chunk=128)
+        one.close()
+        for key in ("order", "points", "ledger", "fastest_car"):
+            assert np.array_equal(tt[key][t * R:(t + 1) * R], tt1[key], equal_nan=True), (name, key)
+            assert np.array_equal(comp[key][t * R:(t + 1) * R], comp1[key], equal_nan=True), (name, key)
+        want.add_time_trial(tt1["order"], tt1["points"])
+        want.add_competition(comp1["order"], comp1["points"], comp1["fastest_car"])
+    assert np.array_equal(table.points, want.points)
+    for key in want.stats:
+        assert np.array_equal(table.stats[key], want.stats[key]), key
+    assert all(np.array_equal(x, y) for x, y in zip(table.standings(), want.standings()))
+    assert table.points.sum() == 2 * R * sum(race.COMPETITION_POINTS[-C:]) + table.stats["fastest_laps"].sum() * 15 \
+        + (table.stats["time_trial_wins"].sum() * 15 + table.stats["time_trial_2nd"].sum() * 7
+           + table.stats["time_trial_3rd"].sum() * 3)
+    assert comp["total_reward"].std() > 0 and (comp["steps"], tt["steps"]) == (700, [300, 300])
+
+
+# ------------------------------------------------------------------ messages
+def test_refusals_carry_the_library_message():
+    env = _engine(2, 3, "martinsville")
+    env.reset()
+    with pytest.raises(RuntimeError, match=r"no race ledger: switch race mode on first \(nascar_set_race\)"):
+        env.race()
+    with pytest.raises(RuntimeError, match=r"race_rank: no ledger given and none on the handle"):
+        env.race_rank(1)
+    with pytest.raises(ValueError, match="race mode must be"):
+        env.set_race(3)
+    with pytest.raises(RuntimeError, match=r"laps_per_attempt must be >= 1"):
+        env.set_race(2, 0)
+    env.set_race(1)
+    with pytest.raises(RuntimeError, match=r"race mode \(nascar_set_race\) needs auto_reset = 0"):
+        env.rollout(1, 2, auto_reset=True)
+    with pytest.raises(RuntimeError, match=r"race mode \(nascar_set_race\) needs auto_reset = 0"):
+        env.step_driven(1, auto_reset=True)
+    env.set_rollout_streams(0)
+    with pytest.raises(RuntimeError, match=r"race mode \(nascar_set_race\) does not run in the fused rollout kernel"):
+        env.rollout(1, 2, auto_reset=False)
+    env.set_rollout_streams(4)
+    env.set_rollout_pipe(2)
+    with pytest.raises(RuntimeError, match=r"race mode \(nascar_set_race\) does not run in the pipelined rollout"):
+        env.rollout(1, 2, auto_reset=False)
+    env.set_rollout_pipe(0)
+    env.set_random_tracks([_track("daytona"), _track("martinsville")], seeds=[1, 2])
+    with pytest.raises(RuntimeError, match=r"race mode \(nascar_set_race\) is not available in random-track mode"):
+        env.rollout(1, 2, auto_reset=False)
+    env.clear_random_tracks()
+    env.reset()
+    env.set_fitness(True)                       # fitness and race mode may both be on
+    env.rollout(1, 3, auto_reset=False)
+    assert (env.race().ledger[..., F["steps"]] == 3).all() and (env.fitness()[..., 6] == 3).all()
+    env.set_fitness(False)
+    env.set_race(2)
+    for p in (0, 1, 3):
+        with pytest.raises(RuntimeError, match=rf"race mode 2 \(time trial\) parks cars through an action buffer: policy {p} "):
+            env.rollout(p, 2, auto_reset=False)
+    with pytest.raises(RuntimeError, match=r"race mode 2 \(time trial\) parks cars through an action buffer: policy 1 "):
+        env.step_driven(1, auto_reset=False)
+    with pytest.raises(RuntimeError, match=r"race_rank: mode must be 1"):
+        env.race_rank(0)
+    with pytest.raises(RuntimeError, match=r"race_rank: the handle's ledger holds 2 envs of 3 cars"):
+        _lib.check(env.L.nascar_race_rank(env.h, None, None, 3, 3, 1, None, None, None, None))
+    env.set_race(0)
+    env.rollout(1, 2, auto_reset=True)          # off again: nothing changes for existing callers
+    env.close()
+
+
+def test_collect_refuses_race_mode():
+    from nascargymnasium_amd import policy as P
+    from nascargymnasium_amd.offpolicy import ReplayBuffer
+    env = _engine(2, 3, "martinsville")
+    env.reset()
+    env.set_actor_critic(P.random_actor_critic(64, 64))
+    d = np.load(os.path.join(GOLDEN, "sac_1235_actor.npz"))
+    w = {k: d[k.replace(".", "__")] for k in P.ACTOR_KEYS}
+    env.set_explorer(P.make_controller([w[k] for k in P.ACTOR_KEYS], P.RELU, P.OUT_SQUASH, "sac"), sigma=(0.1, 0.1))
+    env.set_race(1)
+    with pytest.raises(RuntimeError, match=r"collect steps with auto-reset: switch race mode off \(nascar_set_race"):
+        env.collect(2)
+    with pytest.raises(RuntimeError, match=r"collect_transitions steps with auto-reset: switch race mode off \(nascar_set_race"):
+        env.collect_transitions(ReplayBuffer(env, 4), 2)
+    env.set_race(0)
+    env.collect(2)
+    env.close()
