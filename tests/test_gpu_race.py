@@ -245,9 +245,10 @@ def test_competition_ledger_26x10():
     of the martinsville envs hold a lap and no daytona car does, and 24 cars are disabled.  No env of this field ends
     (4200 oracle steps, two seeds): the slots are the same in every env, so the idle env's rule and noisy cars keep
     driving after its genome cars are disabled.  The env that ends early is test_competition_ledger_26x10_idle_env's.
-    Known limit: the ledger's frozen-after-end path is therefore exercised with genome slots only (there, and at 5 x 1),
-    not together with rule and noisy slots or lap events; the only end a mixed field reaches is the truncation at
-    180 s, 10800 steps, which ends every env at once."""
+    The ledger's frozen-after-end path is therefore exercised here with genome slots only (there, and at 5 x 1); an env
+    that ends after lap events, beside one that races on, is tests/test_gpu_race_mlp.py's
+    test_competition_ends_an_env_after_lap_events (trained SAC / PPO / A2C cars on nascar2).  The only end this field
+    reaches is the truncation at 180 s, 10800 steps, which ends every env at once."""
     E, C, K = 26, 10, COMPETITION_K
     led, fastest, ended_at = _competition_case(E, C, MIXED_TRACKS, K, 12)
     print("envs ended at", ended_at, "fastest", fastest.tolist())
