@@ -3509,13 +3509,6 @@ static int rt_block_map(NascarHandle* h, hipStream_t s, int force) {
   HIPCHK(hipGetLastError());
   return 0;
 }
-// random-track mode, after a step with auto-reset (env_flags: that step's, non-null): the reset envs draw their next
-// tracks, the switching ones are reset there (rt_switch_kernel), and the block map follows
-static int rt_after_step(NascarHandle* h, const Params& P, const uint8_t* env_flags, float* obs, hipStream_t s) {
-  hipLaunchKernelGGL(rt_switch_kernel, dim3((h->E + 63) / 64), dim3(RT_SWITCH_BLOCK), 0, s, P, rt_dev(h), env_flags, obs);
-  HIPCHK(hipGetLastError());
-  return rt_block_map(h, s, 0);
-}
 
 extern "C" int nascar_reset(NascarHandle* h, const uint8_t* env_mask, float* obs, void* stream) {
   if (!h || !obs) return fail("null argument");
@@ -3542,17 +3535,17 @@ extern "C" int nascar_reset(NascarHandle* h, const uint8_t* env_mask, float* obs
 // obs_in: the observation the device driver reads (the previous step's); obs: where this step's is written
 // phases: which of the three launches to enqueue (bit 0 model (+ car contact), bit 1 logic, bit 2 sensors), so
 // the sharded rollout can enqueue one phase for every shard before the next phase (see rollout_sharded)
-enum { PH_MODEL = 1, PH_LOGIC = 2, PH_SENSOR = 4, PH_ALL = 7 };
+enum { PH_MODEL = 1, PH_LOGIC = 2, PH_SENSOR = 4 };
 static int launch_step_range(NascarHandle* h, const Params& P, int nb, const void* actions, int32_t discrete, int policy,
                              uint64_t seed, int64_t step, const float* obs_in, float* obs, float* reward,
                              uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs,
-                             hipStream_t s, int phases = PH_ALL, bool model_issued = false) {
+                             hipStream_t s, int phases, bool model_issued) {
   const bool timed = h->step_ev[0] && nb == h->nblocks;   // nascar_set_step_events: whole-grid steps only
   if (h->fuse_ml) {   // model + logic in one launch (model_logic_kernel); logic is part of PH_MODEL
     // Under the fused kernel the logic phase IS part of PH_MODEL's launch, so a PH_LOGIC-only request enqueues nothing:
     // only a caller that has already requested PH_MODEL for the same step and range may make it (model_issued: the
-    // sharded rollout's phase-major loop, 1 << ph for ph = 0, 1, 2); anyone else gets an error, not a silently
-    // skipped env logic.  nascar_step / nascar_step_driven pass PH_ALL.
+    // shard driver's phase-major loop, 1 << ph for ph = 0, 1, 2, which nascar_step / nascar_step_driven run through too);
+    // anyone else gets an error, not a silently skipped env logic.
     if ((phases & PH_LOGIC) && !(phases & PH_MODEL) && !model_issued)
       return fail("the logic phase alone cannot run under the fused model + logic kernel (nascar_set_fused_logic(h, 0))");
     if (phases & PH_MODEL) {
@@ -3601,17 +3594,7 @@ extern "C" int nascar_set_step_events(NascarHandle* h, void* const* events, int3
   return 0;
 }
 
-// fitness accumulation (nascar_set_fitness) of one step for the cars of workgroups [b0, b1), after their sensor launch
-static int launch_fitness(NascarHandle* h, const Params& P, int b0, int b1, const float* reward, const uint8_t* env_flags,
-                          hipStream_t s) {
-  const int nslot = (b1 - b0) * h->epb, epw = 256 / h->C;
-  if (nslot <= 0) return 0;
-  hipLaunchKernelGGL(fitness_kernel, dim3((nslot + epw - 1) / epw), dim3(256), 0, s, P, b0 * h->epb, nslot, reward, env_flags,
-                     h->d_fit, h->d_fit_ended);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-// The accumulators take an env's terminal step and freeze; an auto-reset would put the reset state under that step's
+// The fitness accumulators take an env's terminal step and freeze; an auto-reset would put the reset state under that step's
 // speed and on_track, so the two are refused together (evaluation steps past termination, as the trainer's env does)
 static int fitness_refused(const NascarHandle* h, int auto_reset) {
   if (h->fit_on && auto_reset)
@@ -3621,21 +3604,11 @@ static int fitness_refused(const NascarHandle* h, int auto_reset) {
   return 0;
 }
 // Where a step writes its env flags when the caller passed no buffer: the two readers of a step's flags bring their
-// own, random-track mode's switch after an auto-reset step (rt_after_step) and the fitness accumulators
-// (launch_fitness).  fitness_refused keeps the two apart.
+// own, random-track mode's switch after an auto-reset step and the fitness accumulators (after_step_range).
+// fitness_refused keeps the two apart.
 static uint8_t* step_env_flags(const NascarHandle* h, uint8_t* env_flags, int auto_reset) {
   if (env_flags) return env_flags;
   return h->rt_on && auto_reset ? h->d_rt_flags : h->fit_on ? h->d_fit_flags : h->race_mode ? h->d_race_flags : nullptr;
-}
-// the race ledger (nascar_set_race) of one step for the cars of workgroups [b0, b1), after their sensor launch
-static int launch_race(NascarHandle* h, const Params& P, int b0, int b1, const float* reward, const uint8_t* env_flags,
-                       hipStream_t s) {
-  const int nslot = (b1 - b0) * h->epb, epw = 256 / h->C;
-  if (nslot <= 0) return 0;
-  hipLaunchKernelGGL(race_step_kernel, dim3((nslot + epw - 1) / epw), dim3(256), 0, s, P, b0 * h->epb, nslot, h->race_mode,
-                     h->race_laps, reward, env_flags, h->d_race, h->race_env);
-  HIPCHK(hipGetLastError());
-  return 0;
 }
 // The ledger freezes an env after its last step as the fitness accumulators do, so it refuses what they refuse
 static int race_refused(const NascarHandle* h, int auto_reset) {
@@ -3660,60 +3633,11 @@ static int launch_genome(NascarHandle* h, const Params& P, int b0, int b1, int n
   const int nslot = b0 < 0 ? 0 : (b1 - b0) * h->epb;
   const int lanes = b0 < 0 ? n1 - n0 : nslot * h->C;
   if (lanes <= 0) return 0;
-  if (race_parked(h))
-    hipLaunchKernelGGL(genome_policy_kernel<true>, dim3((lanes + 255) / 256), dim3(256), 0, s, P, b0 < 0 ? -1 : b0 * h->epb,
-                       nslot, n0, n1, slots, obs, act, h->d_ctl, h->d_genome, race_parked(h));
-  else
-    hipLaunchKernelGGL(genome_policy_kernel<false>, dim3((lanes + 255) / 256), dim3(256), 0, s, P, b0 < 0 ? -1 : b0 * h->epb,
-                       nslot, n0, n1, slots, obs, act, h->d_ctl, h->d_genome, (const double*)nullptr);
+  const double* park = race_parked(h);   // the two instantiations share a signature: the mask (null: none) picks one
+  hipLaunchKernelGGL((park ? genome_policy_kernel<true> : genome_policy_kernel<false>), dim3((lanes + 255) / 256), dim3(256), 0,
+                     s, P, b0 < 0 ? -1 : b0 * h->epb, nslot, n0, n1, slots, obs, act, h->d_ctl, h->d_genome, park);
   HIPCHK(hipGetLastError());
   return 0;
-}
-
-static int step_impl(NascarHandle* h, const void* actions, int32_t discrete, int policy, uint64_t seed, int64_t step,
-                     float* obs, float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset,
-                     float* terminal_obs, void* stream) {
-  if (vis_refused(h) || fitness_refused(h, auto_reset) || race_refused(h, auto_reset)) return -1;
-  if (h->race_mode == RACE_TIME_TRIAL && policy >= 0)
-    return fail("race mode 2 (time trial) parks cars through an action buffer: policy %d runs inside the step launch -- use "
-                "nascar_policy_actions + nascar_step, or policy 2, 4 or 5 of nascar_rollout", policy);
-  h->pristine = false;
-  if (prepare(h, (hipStream_t)stream)) return -1;
-  Params P = make_params(h);
-  // Whole grid on the caller's stream: splitting one step over streams needs a fork and a join per step, and
-  // the per-step barrier measured slower than one grid (tools/streams_exp.py: 2 / 4 shards 0.252 / 0.277 ms vs
-  // 0.224 ms).  Shards pay off only when they run many steps unsynchronised: the sharded nascar_rollout.
-  uint8_t* ef = step_env_flags(h, env_flags, auto_reset);
-  if (launch_step_range(h, P, h->nblocks, actions, discrete, policy, seed, step, obs, obs, reward, car_flags, ef, auto_reset,
-                        terminal_obs, (hipStream_t)stream))
-    return -1;
-  if (h->fit_on && launch_fitness(h, P, 0, h->nblocks, reward, ef, (hipStream_t)stream)) return -1;
-  if (h->race_mode && launch_race(h, P, 0, h->nblocks, reward, ef, (hipStream_t)stream)) return -1;
-  return h->rt_on && auto_reset ? rt_after_step(h, P, ef, obs, (hipStream_t)stream) : 0;
-}
-extern "C" int nascar_step(NascarHandle* h, const void* actions, int32_t discrete, float* obs, float* reward,
-                           uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs, void* stream) {
-  if (!h || !actions || !obs || !reward) return fail("null argument");
-  return step_impl(h, actions, discrete, -1, 0, 0, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
-}
-extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, float* obs, float* reward,
-                                  uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs,
-                                  void* stream) {
-  if (!h || !obs || !reward) return fail("null argument");
-  if (policy == 2 || policy == 4)
-    return fail("driven step: policy %d (MLP controllers) runs in launches of its own -- use nascar_policy_actions + nascar_step "
-                "or nascar_rollout", policy);
-  if (policy == 5)
-    return fail("driven step: policy 5 (genome drivers) runs in a launch of its own -- use nascar_policy_actions + nascar_step "
-                "or nascar_rollout");
-  if (policy == 6)
-    return fail("driven step: policy 6 (the sampled actor-critic) runs in launches of its own -- use nascar_policy_actions + "
-                "nascar_step or nascar_collect");
-  if (policy == 7)
-    return fail("driven step: policy 7 (the explorer) runs in a launch of its own -- use nascar_policy_actions + nascar_step "
-                "or nascar_collect_transitions");
-  if (policy != 0 && policy != 1 && policy != 3) return fail("driven step policy must be 0, 1 or 3 (got %d)", policy);
-  return step_impl(h, nullptr, 0, policy, seed, step, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
 }
 
 // Sharded rollout: the workgroups split into S contiguous ranges (shards of whole envs), each stepped `steps`
@@ -3731,19 +3655,12 @@ extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed
 static void launch_actor(NascarHandle* h, int n, const float* obs, float* actions, void* stream);
 static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int64_t step, const float* obs, float* act,
                         hipStream_t s);
-// the buffers of nascar_collect (policy 6 of the sharded rollout): per-step records beside the rollout's own
-struct CollectBufs { float* actions; float* logp; float* values; float* timeout_values; };
 enum { AC_SAMPLE = 1, AC_VALUE = 2 };
 static int launch_ac(NascarHandle* h, int what, int c0, int n, uint64_t seed, int64_t step, const float* obs, float* act,
                      float* actions, float* logp, float* values, const uint8_t* tflags, hipStream_t s);
 // the explorer (policy 7) on the cars [c0, c0 + n): u to act, the scaled buffer action s to s_out (null: not kept)
 static int launch_explorer(NascarHandle* h, int c0, int n, uint64_t seed, int64_t step, const float* obs, float* act,
                            float* s_out, hipStream_t s);
-// the ring of nascar_collect_transitions (the sharded rollout fills slot (pos + k) % capacity at step k) and its source
-struct ReplayRun { NascarReplay R; int pos, source; };
-// nascar_collect_normalized: the engine's raw observation [N][38] (the step runs in place on it) and the raw reward
-// records [steps][N]; the rollout's own obs / reward records take the normalised values
-struct NormRun { float* obs_raw; float* raw_reward; };
 // One VecNormalize.step_wait for the cars [c0, c1) on stream s (defined with nascar_normalize_step); update: the
 // statistics first (whole batch: c0 = 0, c1 = N)
 static int norm_step_range(NascarHandle* h, size_t c0, size_t c1, bool update, const float* obs_raw, const float* reward_raw,
@@ -3760,6 +3677,43 @@ static ShardRange shard_range(const NascarHandle* h, int s, int S) {
   if (S == 1) return {b0, b1, 0, (size_t)h->N};
   const size_t E = (size_t)h->E;
   return {b0, b1, std::min((size_t)b0 * h->epb, E) * h->C, std::min((size_t)b1 * h->epb, E) * h->C};
+}
+// What an action launch records beside the action that steps the envs (null: not kept).  nascar_collect: a ~ N(mu, std) and
+// V on the step's observation into actions / logp / values [k]; nascar_collect_transitions: the scaled action into its slot.
+struct ActRecords { float* actions; float* logp; float* values; };
+// One step's buffers, whole batch: a mode of the sharded rollout names them once per step (its io(k)); the step's launches
+// and every consumer of its outputs read them from here, so none can read another buffer than the one the step wrote.
+struct StepIO {
+  const float* act_obs;            // the observation the action launch reads
+  float* obs_in; float* obs_out;   // launch_step_range's obs_in (the in-launch driver's observation) and obs (written)
+  float* reward; uint8_t* car_flags; uint8_t* env_flags;
+  float* term;                     // the terminal-observation scratch (null: none wanted)
+  ActRecords rec;
+  float* norm_obs; float* norm_reward;   // where a normalisation after the step writes (null: none)
+};
+// step k (the last one? its absolute index; the call's seed) of shard range r on stream st
+struct ShardStep { int k; bool last; int64_t step; uint64_t seed; const StepIO& io; ShardRange r; hipStream_t st; };
+// The consumers of a finished step, after its range's sensor launch: the fitness accumulators (nascar_set_fitness) and the
+// race ledger (nascar_set_race) for the cars of the range's workgroups, then random-track mode's switch for the batch
+static int after_step_range(NascarHandle* h, const Params& P, const ShardStep& x, int auto_reset) {
+  const int slot0 = x.r.b0 * h->epb, nslot = (x.r.b1 - x.r.b0) * h->epb, epw = 256 / h->C;
+  if (h->fit_on && nslot > 0) {
+    hipLaunchKernelGGL(fitness_kernel, dim3((nslot + epw - 1) / epw), dim3(256), 0, x.st, P, slot0, nslot,
+                       (const float*)x.io.reward, (const uint8_t*)x.io.env_flags, h->d_fit, h->d_fit_ended);
+    HIPCHK(hipGetLastError());
+  }
+  if (h->race_mode && nslot > 0) {
+    hipLaunchKernelGGL(race_step_kernel, dim3((nslot + epw - 1) / epw), dim3(256), 0, x.st, P, slot0, nslot, h->race_mode,
+                       h->race_laps, (const float*)x.io.reward, (const uint8_t*)x.io.env_flags, h->d_race, h->race_env);
+    HIPCHK(hipGetLastError());
+  }
+  if (!h->rt_on || !auto_reset) return 0;
+  // random-track mode runs one range, the whole grid, on the caller's stream: after a step with auto-reset the reset envs
+  // draw their next tracks, the switching ones are reset there (rt_switch_kernel), and the block map follows
+  hipLaunchKernelGGL(rt_switch_kernel, dim3((h->E + 63) / 64), dim3(RT_SWITCH_BLOCK), 0, x.st, P, rt_dev(h),
+                     (const uint8_t*)x.io.env_flags, x.io.obs_out);
+  HIPCHK(hipGetLastError());
+  return rt_block_map(h, x.st, 0);
 }
 // Policies 2 (the SAC actor), 4 (the field of controllers), 5 (genome drivers) and 6 (the sampled actor-critic) produce
 // their actions in launches of their own.  policy_ready: what such a launch needs of the handle and of the buffers it
@@ -3786,15 +3740,15 @@ static int policy_ready(const NascarHandle* h, int policy, const float* obs, con
 }
 // launch_actions: policy 2, 4, 5 or 6 for the cars of r on stream s, obs ([N][38]) to act ([N][2]).  The genome driver
 // walks r's workgroups in the block map, which need not be the identity, or r's cars where r has no workgroups.
-// Policy 6 with rec (nascar_collect): the step's actions, logp and values records too.
+// Policy 6 with a values record (nascar_collect): V on the same observation too.
 static int launch_actions(NascarHandle* h, int policy, const Params& P, const ShardRange& r, uint64_t seed, int64_t step,
-                          const float* obs, float* act, const CollectBufs* rec, hipStream_t s) {
+                          const float* obs, float* act, const ActRecords& rec, hipStream_t s) {
   const int c0 = (int)r.c0, n = (int)(r.c1 - r.c0);
   // (policies 6 and 7 are the learners' sampling sources: collection refuses race mode, and they are not masked)
-  if (policy == 7) return launch_explorer(h, c0, n, seed, step, obs, act, rec ? rec->actions : nullptr, s);
+  if (policy == 7) return launch_explorer(h, c0, n, seed, step, obs, act, rec.actions, s);
   if (policy == 6)
-    return launch_ac(h, rec ? AC_SAMPLE | AC_VALUE : AC_SAMPLE, c0, n, seed, step, obs, act, rec ? rec->actions : nullptr,
-                     rec ? rec->logp : nullptr, rec ? rec->values : nullptr, nullptr, s);
+    return launch_ac(h, rec.values ? AC_SAMPLE | AC_VALUE : AC_SAMPLE, c0, n, seed, step, obs, act, rec.actions, rec.logp,
+                     rec.values, nullptr, s);
   if (policy == 5) return launch_genome(h, P, r.b0, r.b1, c0, (int)r.c1, ~0ull, obs, act, s);
   if (policy == 4) return launch_field(h, c0 / h->C, n / h->C, seed, step, obs, act, s);
   if (n > 0) launch_actor(h, n, obs + r.c0 * 38, act + r.c0 * 2, s);
@@ -3830,124 +3784,55 @@ static int upload_params(NascarHandle* h, const Params& P, hipStream_t stream) {
   }
   return 0;
 }
-static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed, int64_t step0, int32_t steps, float* obs,
-                           float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, int32_t traj,
-                           hipStream_t stream, const CollectBufs* col = nullptr, const ReplayRun* rp = nullptr,
-                           const NormRun* nr = nullptr) {
-  S = std::max(1, std::min(S, h->nblocks));
-  // running statistics: step k + 1 is normalised with every env's step-k observation, so the batch steps as one shard
-  // (frozen statistics are row-local: the shards keep running unsynchronised)
-  if (nr && norm_updates(h)) S = 1;
-  const bool rt = h->rt_on && auto_reset;
-  if (h->rt_on) S = 1;   // random-track mode: the block map changes between steps, so no shard owns a fixed set of envs
-  // the actions come from a launch of their own (launch_actions; the callers have checked policy_ready), into d_ro_act
-  const bool actor = policy == 2 || policy == 4 || policy == 5 || policy == 6 || policy == 7;
-  if (rp) {   // nascar_collect_transitions: a shard's cars must be contiguous, whatever the source
-    if (!h->map_identity) S = 1;
-    if (!h->d_term) HIPCHK(hipMalloc(&h->d_term, sizeof(float) * 38 * (size_t)h->N));
-    if (!h->d_rp_cf) {
-      HIPCHK(hipMalloc(&h->d_rp_cf, (size_t)h->N + (size_t)h->E));
-      h->d_rp_ef = h->d_rp_cf + h->N;
-    }
-  }
-  if (actor) {
-    if (col && !h->d_term) HIPCHK(hipMalloc(&h->d_term, sizeof(float) * 38 * (size_t)h->N));
-    if (!h->map_identity && policy != 5) S = 1;   // the genome driver walks its shard's env slots of the block map
-    if (!h->d_ro_act) HIPCHK(hipMalloc(&h->d_ro_act, sizeof(float) * 2 * (size_t)h->N));
-  }
+// A mode of the sharded rollout gives io(k), step k's buffers, and may redefine these hooks (the defaults do nothing).  The
+// modes are plain structs next to their entry points and the driver a template on them: no indirect call in the step loop.
+struct StepHooks {
+  bool one_shard(const NascarHandle*) const { return false; }              // the mode's own reason to step the batch as one shard
+  int after_sensors(NascarHandle*, const ShardStep&) const { return 0; }   // on the shard's stream, after its sensor launch
+  int after_step(NascarHandle*, const ShardStep&) const { return 0; }      // per shard, once step k of every shard is enqueued
+};
+// The shards of a call: at most one per workgroup.  One in random-track mode (the block map changes between steps, so no
+// shard owns a fixed set of envs) and where an action launch takes its shard's cars as one run of rows under a map that is
+// not the identity (rows_launch: all but the genome driver's, which walks its shard's env slots of the block map)
+static int shard_count(const NascarHandle* h, int S, bool rows_launch, bool mode_one_shard) {
+  if (mode_one_shard || h->rt_on || (rows_launch && !h->map_identity)) return 1;
+  return std::max(1, std::min(S, h->nblocks));
+}
+// The shard driver: `steps` steps on mode m's buffers, the actions from the caller's buffer (policy < 0), from inside the
+// step launch (policies 0, 1, 3) or from launch_actions into d_ro_act (2, 4, 5, 6, 7; the callers have checked policy_ready)
+template <class Mode>
+static int rollout_sharded(NascarHandle* h, int S, const Mode& m, const void* actions, int32_t discrete, int32_t policy,
+                           uint64_t seed, int64_t step0, int32_t steps, int32_t auto_reset, hipStream_t stream) {
+  const bool actor = policy == 2 || (policy >= 4 && policy <= 7);
+  S = shard_count(h, S, actor && policy != 5, m.one_shard(h));
+  if (actor && !h->d_ro_act) HIPCHK(hipMalloc(&h->d_ro_act, sizeof(float) * 2 * (size_t)h->N));
   if (S > 1 && ensure_shard_streams(h, S - 1, "the rollout shard streams")) return -1;
   auto shard_stream = [&](int s) { return s == 0 ? stream : h->sub_stream[s - 1]; };
-  const Params P0 = make_params(h);
-  if (S > 1) {
-    HIPCHK(hipEventRecord(h->ev_fork, stream));
-    for (int s = 1; s < S; ++s) HIPCHK(hipStreamWaitEvent(shard_stream(s), h->ev_fork, 0));
-  }
-  const size_t NC = (size_t)h->N, E = (size_t)h->E;
-  const bool obs_traj = (traj & NASCAR_TRAJ_OBS) != 0;   // obs = [steps + 1][N][38]: record 0 in, record k + 1 out
+  Params P = make_params(h);   // (blk0: each shard's first workgroup)
+  if (S > 1) HIPCHK(hipEventRecord(h->ev_fork, stream));
+  for (int s = 1; s < S; ++s) HIPCHK(hipStreamWaitEvent(shard_stream(s), h->ev_fork, 0));
   auto enqueue = [&]() -> int {
     for (int k = 0; k < steps; ++k) {
-      const size_t ko = traj ? (size_t)k : 0;
-      float* o_in = obs_traj ? obs + (size_t)k * NC * 38 : obs;
-      float* o_out = obs_traj ? obs + (size_t)(k + 1) * NC * 38 : obs;
-      // normalised collection: the actor-critic reads record k, the step runs in place on the raw observation, and
-      // record k + 1 is written by the normalisation after the step
-      float* a_in = o_in;
-      float* n_out = o_out;
-      if (nr) o_in = o_out = nr->obs_raw;
-      uint8_t* ef = rp ? h->d_rp_ef : step_env_flags(h, env_flags ? env_flags + ko * E : nullptr, auto_reset);
-      // nascar_collect_transitions: the step runs in place on obs and writes its reward into the ring's slot; the
-      // explorer writes the slot's scaled action beside the action that steps the envs
-      const size_t slot = rp ? (size_t)((rp->pos + (int64_t)k) % rp->R.capacity) : 0;
-      const size_t slot1 = rp ? (slot + 1) % (size_t)rp->R.capacity : 0;
-      float* rew_k = rp ? rp->R.reward + slot * NC : nr ? nr->raw_reward + ko * NC : reward + ko * NC;
-      uint8_t* cf_k = rp ? h->d_rp_cf : car_flags ? car_flags + ko * NC : nullptr;
-      float* term_k = col || rp ? h->d_term : nullptr;
-      const CollectBufs rrec = rp ? CollectBufs{rp->R.actions + 2 * slot * NC, nullptr, nullptr, nullptr} : CollectBufs{};
-      // one transition of shard range r, after its sensors (random-track mode: after the track switch)
-      auto store = [&](const ShardRange& r, hipStream_t st) -> int {
-        const long long lanes = (long long)(r.c1 - r.c0) * RP_ROW;
-        if (lanes <= 0) return 0;
-        hipLaunchKernelGGL(replay_store_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, (int)r.c0, (int)r.c1,
-                           h->C, (const float*)o_out, (const float*)h->d_term, (const uint8_t*)h->d_rp_cf,
-                           (const uint8_t*)h->d_rp_ef, rp->R.next_obs + slot * NC * 38,
-                           k + 1 < steps ? rp->R.obs + slot1 * NC * 38 : nullptr, rp->R.done + slot * NC,
-                           rp->R.timeout + slot * NC, rp->R.live + slot * NC, rp->R.actions + 2 * slot * NC, rp->source, seed,
-                           step0 + k);
-        HIPCHK(hipGetLastError());
-        return 0;
-      };
-      // nascar_collect: a ~ N(mu, std) and V on the step's observation into actions / logp / values [k]; clip(a) drives the step
-      // (a categorical actor's action record is one int32 index per car behind the same pointer, not a float pair)
-      const size_t act_w = col && h->ctrl[h->ac_pi].output == MLP_OUT_CATEGORICAL ? 1 : 2;
-      const CollectBufs rec = col ? CollectBufs{col->actions + act_w * ko * NC, col->logp + ko * NC, col->values + ko * NC, nullptr}
-                                  : CollectBufs{};
+      StepIO io = m.io(h, k);
+      io.env_flags = step_env_flags(h, io.env_flags, auto_reset);
       // phase-major enqueue (every shard's model launch, then every shard's logic, then sensors): each stream's
       // order is unchanged, but a shard's first launch of the call is queued ~6 us (one launch) after the previous
-      // shard's instead of ~18 us (three), so the shards start together
-      for (int ph = 0; ph < 3; ++ph) {
+      // shard's instead of ~18 us (three), so the shards start together.  A fourth pass: the mode's after-step work.
+      for (int ph = 0; ph < 4; ++ph) {
         for (int s = 0; s < S; ++s) {
-          const ShardRange r = shard_range(h, s, S);
-          Params P = P0;
-          P.blk0 = r.b0;
-          if (rp && k == 0 && ph == 0 && r.c1 > r.c0)   // the first slot's obs rows: the observation on entry
-            HIPCHK(hipMemcpyAsync(rp->R.obs + (slot * NC + r.c0) * 38, obs + r.c0 * 38, sizeof(float) * 38 * (r.c1 - r.c0),
-                                  hipMemcpyDeviceToDevice, shard_stream(s)));
-          if (actor && ph == 0 &&
-              launch_actions(h, policy, P, r, seed, step0 + k, a_in, h->d_ro_act, col ? &rec : rp ? &rrec : nullptr,
-                             shard_stream(s)))
+          const ShardStep x{k, k + 1 == steps, step0 + k, seed, io, shard_range(h, s, S), shard_stream(s)};
+          P.blk0 = x.r.b0;
+          if (ph == 0 && actor && launch_actions(h, policy, P, x.r, seed, x.step, io.act_obs, h->d_ro_act, io.rec, x.st))
             return -1;
-          if (launch_step_range(h, P, r.b1 - r.b0, actor ? h->d_ro_act : nullptr, 0, actor ? -1 : policy, seed, step0 + k,
-                                o_in, o_out, rew_k, cf_k, ef, auto_reset, term_k, shard_stream(s), 1 << ph, ph == 1))
+          if (ph < 3 && launch_step_range(h, P, x.r.b1 - x.r.b0, actor ? h->d_ro_act : actions, actor ? 0 : discrete,
+                                          actor ? -1 : policy, seed, x.step, io.obs_in, io.obs_out, io.reward, io.car_flags,
+                                          io.env_flags, auto_reset, io.term, x.st, 1 << ph, ph == 1))
             return -1;
-          if (rp && ph == 2 && !rt && store(r, shard_stream(s))) return -1;
-          // SB3's time-limit bootstrap: V(terminal obs) for the cars of truncated, not terminated envs
-          if (col && ph == 2 && !nr &&
-              launch_ac(h, AC_VALUE, (int)r.c0, (int)(r.c1 - r.c0), seed, step0 + k, h->d_term, nullptr, nullptr, nullptr,
-                        col->timeout_values + ko * NC, ef, shard_stream(s)))
-            return -1;
-          if (h->fit_on && ph == 2 && launch_fitness(h, P, r.b0, r.b1, reward + ko * NC, ef, shard_stream(s))) return -1;
-          if (h->race_mode && ph == 2 && launch_race(h, P, r.b0, r.b1, reward + ko * NC, ef, shard_stream(s))) return -1;
+          if (ph == 2 && (m.after_sensors(h, x) || after_step_range(h, P, x, auto_reset))) return -1;
+          if (ph == 3 && m.after_step(h, x)) return -1;
         }
       }
-      if (rt && rt_after_step(h, P0, ef, o_out, stream)) return -1;
-      if (rp && rt && store(shard_range(h, 0, 1), stream)) return -1;
-      if (nr)   // VecNormalize.step_wait on the step's raw outputs, then the time-limit values of the normalised terminal rows
-        for (int s = 0; s < S; ++s) {
-          const ShardRange r = shard_range(h, s, S);
-          if (norm_step_range(h, r.c0, r.c1, norm_updates(h), o_out, rew_k, ef, h->d_term, n_out, reward + ko * NC, h->d_term,
-                              shard_stream(s)) ||
-              launch_ac(h, AC_VALUE, (int)r.c0, (int)(r.c1 - r.c0), seed, step0 + k, h->d_term, nullptr, nullptr, nullptr,
-                        col->timeout_values + ko * NC, ef, shard_stream(s)))
-            return -1;
-        }
     }
-    if (col)   // values [steps]: V of the observation after the last step, the bootstrap of the last record
-      for (int s = 0; s < S; ++s) {
-        const ShardRange r = shard_range(h, s, S);
-        if (launch_ac(h, AC_VALUE, (int)r.c0, (int)(r.c1 - r.c0), seed, step0 + steps, obs + (size_t)steps * NC * 38, nullptr,
-                      nullptr, nullptr, col->values + (size_t)steps * NC, nullptr, shard_stream(s)))
-          return -1;
-      }
     return 0;
   };
   const int rc = enqueue();
@@ -3960,6 +3845,58 @@ static int rollout_sharded(NascarHandle* h, int S, int32_t policy, uint64_t seed
     if (e2 != hipSuccess && !jrc && !rc) jrc = fail("joining rollout shard %d failed: %s", s, hipGetErrorString(e2));
   }
   return rc ? rc : jrc;
+}
+
+// nascar_rollout's buffers: with the per-step records (traj) step k writes record k, without them every step writes the one
+// record.  One step of the same, with a terminal-observation buffer: nascar_step / nascar_step_driven.
+struct RolloutRun : StepHooks {
+  float* obs; float* reward; uint8_t* car_flags; uint8_t* env_flags; float* term; int32_t traj;
+  StepIO io(const NascarHandle* h, int k) const {
+    const size_t NC = (size_t)h->N, ko = traj ? (size_t)k : 0;
+    const bool obs_traj = (traj & NASCAR_TRAJ_OBS) != 0;   // obs = [steps + 1][N][38]: record 0 in, record k + 1 out
+    float* o_in = obs_traj ? obs + (size_t)k * NC * 38 : obs;
+    return {o_in, o_in, obs_traj ? o_in + NC * 38 : obs, reward + ko * NC, car_flags ? car_flags + ko * NC : nullptr,
+            env_flags ? env_flags + ko * (size_t)h->E : nullptr, term, ActRecords{}};
+  }
+};
+static int step_impl(NascarHandle* h, const void* actions, int32_t discrete, int policy, uint64_t seed, int64_t step,
+                     float* obs, float* reward, uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset,
+                     float* terminal_obs, void* stream) {
+  if (vis_refused(h) || fitness_refused(h, auto_reset) || race_refused(h, auto_reset)) return -1;
+  if (h->race_mode == RACE_TIME_TRIAL && policy >= 0)
+    return fail("race mode 2 (time trial) parks cars through an action buffer: policy %d runs inside the step launch -- use "
+                "nascar_policy_actions + nascar_step, or policy 2, 4 or 5 of nascar_rollout", policy);
+  h->pristine = false;
+  if (prepare(h, (hipStream_t)stream)) return -1;
+  // One step as ONE shard, the whole grid on the caller's stream: splitting one step over streams needs a fork and a join
+  // per step, and the per-step barrier measured slower than one grid (tools/streams_exp.py: 2 / 4 shards 0.252 / 0.277 ms
+  // vs 0.224 ms).  Shards pay off only when they run many steps unsynchronised: the sharded nascar_rollout.
+  const RolloutRun one{{}, obs, reward, car_flags, env_flags, terminal_obs, 0};
+  return rollout_sharded(h, 1, one, actions, discrete, policy, seed, step, 1, auto_reset, (hipStream_t)stream);
+}
+extern "C" int nascar_step(NascarHandle* h, const void* actions, int32_t discrete, float* obs, float* reward,
+                           uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs, void* stream) {
+  if (!h || !actions || !obs || !reward) return fail("null argument");
+  return step_impl(h, actions, discrete, -1, 0, 0, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
+}
+extern "C" int nascar_step_driven(NascarHandle* h, int32_t policy, uint64_t seed, int64_t step, float* obs, float* reward,
+                                  uint8_t* car_flags, uint8_t* env_flags, int32_t auto_reset, float* terminal_obs,
+                                  void* stream) {
+  if (!h || !obs || !reward) return fail("null argument");
+  if (policy == 2 || policy == 4)
+    return fail("driven step: policy %d (MLP controllers) runs in launches of its own -- use nascar_policy_actions + nascar_step "
+                "or nascar_rollout", policy);
+  if (policy == 5)
+    return fail("driven step: policy 5 (genome drivers) runs in a launch of its own -- use nascar_policy_actions + nascar_step "
+                "or nascar_rollout");
+  if (policy == 6)
+    return fail("driven step: policy 6 (the sampled actor-critic) runs in launches of its own -- use nascar_policy_actions + "
+                "nascar_step or nascar_collect");
+  if (policy == 7)
+    return fail("driven step: policy 7 (the explorer) runs in a launch of its own -- use nascar_policy_actions + nascar_step "
+                "or nascar_collect_transitions");
+  if (policy != 0 && policy != 1 && policy != 3) return fail("driven step policy must be 0, 1 or 3 (got %d)", policy);
+  return step_impl(h, nullptr, 0, policy, seed, step, obs, reward, car_flags, env_flags, auto_reset, terminal_obs, stream);
 }
 
 // Pipelined rollout (see pipe_step_kernel): the step kernel on the caller's stream, the sensor kernel on the first
@@ -4090,8 +4027,8 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
     return rollout_pipe(h, policy, seed, step0, steps, obs, reward, car_flags, env_flags, auto_reset, traj,
                         (hipStream_t)stream);
   if (h->ro_streams > 0)
-    return rollout_sharded(h, h->ro_streams, policy, seed, step0, steps, obs, reward, car_flags, env_flags, auto_reset,
-                           traj, (hipStream_t)stream);
+    return rollout_sharded(h, h->ro_streams, RolloutRun{{}, obs, reward, car_flags, env_flags, nullptr, traj}, nullptr, 0,
+                           policy, seed, step0, steps, auto_reset, (hipStream_t)stream);
   // ro_streams == 0: the fused rollout_kernel
   if (upload_params(h, make_params(h), (hipStream_t)stream)) return -1;
   // >= 2 float4 per wall of the largest track; the car-car extension's scratch after it
@@ -4102,9 +4039,48 @@ extern "C" int nascar_rollout(NascarHandle* h, int32_t policy, uint64_t seed, in
   return 0;
 }
 
+// nascar_collect (policy 6 of the sharded rollout): an obs trajectory with every record kept, the actor-critic's records
+// beside the rollout's own; clip(a) drives the step.  With obs_raw / raw_reward (nascar_collect_normalized; null: none) the
+// step runs in place on the engine's raw observation [N][38] and writes the raw reward records [steps][N]; the actor-critic
+// still reads record k, and the normalisation after the step writes obs record k + 1 and reward record k.
+struct CollectRun : StepHooks {
+  float* obs; float* reward; uint8_t* car_flags; uint8_t* env_flags; float* actions; float* logp; float* values;
+  float* timeout_values; float* obs_raw; float* raw_reward;
+  // running statistics: step k + 1 is normalised with every env's step-k observation, so the batch steps as one shard
+  // (frozen statistics are row-local: the shards keep running unsynchronised)
+  bool one_shard(const NascarHandle* h) const { return obs_raw && norm_updates(h); }
+  StepIO io(const NascarHandle* h, int k) const {
+    const size_t NC = (size_t)h->N, ko = (size_t)k;
+    // (a categorical actor's action record is one int32 index per car behind the same pointer, not a float pair)
+    const size_t act_w = h->ctrl[h->ac_pi].output == MLP_OUT_CATEGORICAL ? 1 : 2;
+    float* o_in = obs + ko * NC * 38;
+    float* o_out = o_in + NC * 38;
+    float* rew = reward + ko * NC;
+    const ActRecords rec{actions + act_w * ko * NC, logp + ko * NC, values + ko * NC};
+    if (!obs_raw) return {o_in, o_in, o_out, rew, car_flags + ko * NC, env_flags + ko * (size_t)h->E, h->d_term, rec};
+    return {o_in, obs_raw, obs_raw, raw_reward + ko * NC, car_flags + ko * NC, env_flags + ko * (size_t)h->E, h->d_term, rec,
+            o_out, rew};   // the step on the raw buffers, the records for the normalisation
+  }
+  // SB3's time-limit bootstrap: V(terminal obs) for the cars of truncated, not terminated envs
+  int timeout_value(NascarHandle* h, const ShardStep& x) const {
+    return launch_ac(h, AC_VALUE, (int)x.r.c0, (int)(x.r.c1 - x.r.c0), x.seed, x.step, x.io.term, nullptr, nullptr, nullptr,
+                     timeout_values + (size_t)x.k * h->N, x.io.env_flags, x.st);
+  }
+  int after_sensors(NascarHandle* h, const ShardStep& x) const { return obs_raw ? 0 : timeout_value(h, x); }
+  // VecNormalize.step_wait on the step's raw outputs, then the time-limit values of the normalised terminal rows
+  int after_step(NascarHandle* h, const ShardStep& x) const {
+    if (obs_raw && (norm_step_range(h, x.r.c0, x.r.c1, norm_updates(h), x.io.obs_out, x.io.reward, x.io.env_flags, x.io.term,
+                                    x.io.norm_obs, x.io.norm_reward, x.io.term, x.st) || timeout_value(h, x)))
+      return -1;
+    if (!x.last) return 0;
+    // values [steps]: V of the observation after the last step, the bootstrap of the last record
+    return launch_ac(h, AC_VALUE, (int)x.r.c0, (int)(x.r.c1 - x.r.c0), x.seed, x.step + 1, obs + (size_t)(x.k + 1) * h->N * 38,
+                     nullptr, nullptr, nullptr, values + (size_t)(x.k + 1) * h->N, nullptr, x.st);
+  }
+};
 static int collect_impl(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps, float* obs, float* reward,
                         uint8_t* car_flags, uint8_t* env_flags, float* actions, float* logp, float* values,
-                        float* timeout_values, const NormRun* nr, void* stream) {
+                        float* timeout_values, float* obs_raw, float* raw_reward, void* stream) {
   if (!h || !obs || !reward || !car_flags || !env_flags || !actions || !logp || !values || !timeout_values)
     return fail("null argument");
   if (steps < 1) return fail("collect: steps must be >= 1 (got %d)", steps);
@@ -4118,15 +4094,15 @@ static int collect_impl(NascarHandle* h, uint64_t seed, int64_t step0, int32_t s
   const bool cat = h->ctrl[h->ac_pi].output == MLP_OUT_CATEGORICAL;   // actions: int32 [steps][E*C], the action index
   if (((uintptr_t)obs | (cat ? 0 : (uintptr_t)actions)) & 7) return fail("collect obs / actions must be 8-byte aligned");
   if ((uintptr_t)actions & 3) return fail("collect actions must be 4-byte aligned");
-  if (nr && ((uintptr_t)nr->obs_raw & 7)) return fail("collect raw obs must be 8-byte aligned");
+  if (obs_raw && ((uintptr_t)obs_raw & 7)) return fail("collect raw obs must be 8-byte aligned");
   if (vis_refused(h)) return -1;
   h->pristine = false;
   if (prepare(h, (hipStream_t)stream)) return -1;
+  if (!h->d_term) HIPCHK(hipMalloc(&h->d_term, sizeof(float) * 38 * (size_t)h->N));   // the terminal rows, for the critic
   // timeout_values is 0 wherever no time limit cut an episode: the value launches write the other records only
   HIPCHK(hipMemsetAsync(timeout_values, 0, sizeof(float) * (size_t)steps * h->N, (hipStream_t)stream));
-  const CollectBufs col{actions, logp, values, timeout_values};
-  return rollout_sharded(h, h->ro_streams, 6, seed, step0, steps, obs, reward, car_flags, env_flags, 1,
-                         NASCAR_TRAJ_RECORDS | NASCAR_TRAJ_OBS, (hipStream_t)stream, &col, nullptr, nr);
+  const CollectRun col{{}, obs, reward, car_flags, env_flags, actions, logp, values, timeout_values, obs_raw, raw_reward};
+  return rollout_sharded(h, h->ro_streams, col, nullptr, 0, 6, seed, step0, steps, 1, (hipStream_t)stream);
 }
 extern "C" int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps, float* obs, float* reward,
                               uint8_t* car_flags, uint8_t* env_flags, float* actions, float* logp, float* values,
@@ -4135,16 +4111,15 @@ extern "C" int nascar_collect(NascarHandle* h, uint64_t seed, int64_t step0, int
     return fail("collect: normalisation is on (nascar_set_normalize): nascar_collect_normalized takes the raw observation "
                 "and the raw reward records beside the normalised ones");
   return collect_impl(h, seed, step0, steps, obs, reward, car_flags, env_flags, actions, logp, values, timeout_values, nullptr,
-                      stream);
+                      nullptr, stream);
 }
 extern "C" int nascar_collect_normalized(NascarHandle* h, uint64_t seed, int64_t step0, int32_t steps, float* obs_raw,
                                          float* obs, float* reward, float* raw_reward, uint8_t* car_flags, uint8_t* env_flags,
                                          float* actions, float* logp, float* values, float* timeout_values, void* stream) {
   if (!h || !obs_raw || !raw_reward) return fail("null argument");
   if (!h->norm_on) return fail("collect_normalized: normalisation is off (nascar_set_normalize): use nascar_collect");
-  const NormRun nr{obs_raw, raw_reward};
-  return collect_impl(h, seed, step0, steps, obs, reward, car_flags, env_flags, actions, logp, values, timeout_values, &nr,
-                      stream);
+  return collect_impl(h, seed, step0, steps, obs, reward, car_flags, env_flags, actions, logp, values, timeout_values, obs_raw,
+                      raw_reward, stream);
 }
 // Off-policy collection (include/nascar.h): `steps` x (source 7 or 0 on the current obs + CarEnv.step with auto-reset) on
 // the sharded rollout, every step's transition written into the caller's ring by the shard that stepped it
@@ -4158,6 +4133,29 @@ static int replay_check(const NascarHandle* h, const NascarReplay* R, const char
   (void)h;
   return 0;
 }
+// The ring of nascar_collect_transitions and its source: step k fills slot (pos + k) % capacity.  The step runs in place on
+// obs and writes its reward into the slot; the explorer writes the slot's scaled action beside the action that steps the envs
+struct TransitionsRun : StepHooks {
+  NascarReplay R; int pos, source; float* obs;
+  bool one_shard(const NascarHandle* h) const { return !h->map_identity; }   // whatever the source, a shard's cars are one run
+  size_t slot(int k) const { return (size_t)((pos + (int64_t)k) % R.capacity); }
+  StepIO io(const NascarHandle* h, int k) const {
+    const size_t at = slot(k) * (size_t)h->N;
+    return {obs, obs, obs, R.reward + at, h->d_rp_cf, h->d_rp_ef, h->d_term, ActRecords{R.actions + 2 * at, nullptr, nullptr}};
+  }
+  // one transition of the shard's cars, after its sensors (random-track mode: after the track switch, as the one shard)
+  int after_step(NascarHandle* h, const ShardStep& x) const {
+    const long long lanes = (long long)(x.r.c1 - x.r.c0) * RP_ROW;
+    if (lanes <= 0) return 0;
+    const size_t NC = (size_t)h->N, at = slot(x.k) * NC, next = (slot(x.k) + 1) % (size_t)R.capacity * NC;
+    hipLaunchKernelGGL(replay_store_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, x.st, (int)x.r.c0,
+                       (int)x.r.c1, h->C, (const float*)x.io.obs_out, (const float*)x.io.term, (const uint8_t*)x.io.car_flags,
+                       (const uint8_t*)x.io.env_flags, R.next_obs + at * 38, x.last ? nullptr : R.obs + next * 38,
+                       R.done + at, R.timeout + at, R.live + at, x.io.rec.actions, source, x.seed, x.step);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+};
 extern "C" int nascar_collect_transitions(NascarHandle* h, int32_t source, uint64_t seed, int64_t step0, int32_t steps,
                                           float* obs, const NascarReplay* replay, int32_t pos, void* stream) {
   if (!h || !obs) return fail("null argument");
@@ -4183,9 +4181,16 @@ extern "C" int nascar_collect_transitions(NascarHandle* h, int32_t source, uint6
   if (vis_refused(h)) return -1;
   h->pristine = false;
   if (prepare(h, (hipStream_t)stream)) return -1;
-  const ReplayRun rp{*replay, pos, source};
-  return rollout_sharded(h, h->ro_streams, source, seed, step0, steps, obs, nullptr, nullptr, nullptr, 1, 0,
-                         (hipStream_t)stream, nullptr, &rp);
+  if (!h->d_term) HIPCHK(hipMalloc(&h->d_term, sizeof(float) * 38 * (size_t)h->N));
+  if (!h->d_rp_cf) {   // the step's terminal rows, car and env flags go to scratch, for the store
+    HIPCHK(hipMalloc(&h->d_rp_cf, (size_t)h->N + (size_t)h->E));
+    h->d_rp_ef = h->d_rp_cf + h->N;
+  }
+  const TransitionsRun run{{}, *replay, pos, source, obs};
+  // the first slot's obs rows: the observation on entry (before the shards fork, so ahead of every shard's first launch)
+  HIPCHK(hipMemcpyAsync(replay->obs + run.slot(0) * (size_t)h->N * 38, obs, sizeof(float) * 38 * (size_t)h->N,
+                        hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return rollout_sharded(h, h->ro_streams, run, nullptr, 0, source, seed, step0, steps, 1, (hipStream_t)stream);
 }
 extern "C" int nascar_replay_sample(NascarHandle* h, const NascarReplay* replay, int32_t size, uint64_t seed, int64_t draw,
                                     int32_t batch, float* obs, float* next_obs, float* actions, float* reward, float* done,
@@ -4622,16 +4627,13 @@ extern "C" int nascar_policy_actions(NascarHandle* h, int32_t policy, uint64_t s
   if (policy >= 1 && !obs) return fail("policy %d needs obs", policy);
   if (policy == 2 || policy >= 4) {   // the whole batch, by its cars
     if (policy_ready(h, policy, obs, actions)) return -1;
-    return launch_actions(h, policy, make_params(h), ShardRange{-1, 0, 0, (size_t)h->N}, seed, step, obs, actions, nullptr,
+    return launch_actions(h, policy, make_params(h), ShardRange{-1, 0, 0, (size_t)h->N}, seed, step, obs, actions, ActRecords{},
                           (hipStream_t)stream);
   }
   int nb = (h->N + 255) / 256;
-  if (race_parked(h))
-    hipLaunchKernelGGL(policy_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, h->N, policy, seed, step, obs, actions,
-                       h->d_ctl, race_parked(h));
-  else
-    hipLaunchKernelGGL(policy_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, h->N, policy, seed, step, obs, actions,
-                       h->d_ctl, (const double*)nullptr);
+  const double* park = race_parked(h);
+  hipLaunchKernelGGL((park ? policy_kernel<true> : policy_kernel<false>), dim3(nb), dim3(256), 0, (hipStream_t)stream, h->N,
+                     policy, seed, step, obs, actions, h->d_ctl, park);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -5058,12 +5060,9 @@ static int launch_field(NascarHandle* h, int env0, int nenv, uint64_t seed, int6
   if (builtin) {
     FieldCodes F{};
     for (int c = 0; c < C; ++c) F.code[c] = (signed char)std::max(h->field[c], NASCAR_CTRL_GENOME);   // the lowest code
-    if (race_parked(h))
-      hipLaunchKernelGGL(field_policy_kernel<true>, dim3((n1 - n0 + 255) / 256), dim3(256), 0, s, n0, n1, C, F, seed, step, obs,
-                         act, h->d_ctl, race_parked(h));
-    else
-      hipLaunchKernelGGL(field_policy_kernel<false>, dim3((n1 - n0 + 255) / 256), dim3(256), 0, s, n0, n1, C, F, seed, step,
-                         obs, act, h->d_ctl, (const double*)nullptr);
+    const double* park = race_parked(h);
+    hipLaunchKernelGGL((park ? field_policy_kernel<true> : field_policy_kernel<false>), dim3((n1 - n0 + 255) / 256), dim3(256),
+                       0, s, n0, n1, C, F, seed, step, obs, act, h->d_ctl, park);
     HIPCHK(hipGetLastError());
   }
   return 0;

@@ -398,3 +398,55 @@ def test_oracle_continues_from_gpu_mid_episode_state():
         contact += int(((gcf & 4) != 0).sum())
     orc.close(); env.close()
     assert contact > 0
+
+
+@pytest.mark.parametrize("fused", [True, False])
+def test_step_events_recorded_and_results_unchanged(fused):
+    """set_step_events: whole-grid steps record the four events in order (before the model launch, after it, after the
+    logic, after the sensors) under the fused and the split logic, through launch_step and through a one-stream rollout.
+    set_step_events itself records fresh events once, so each part puts a marker on the stream first: the engine's
+    records must lie behind it, every interval defined and >= 0, and the four span the kernels (> 0).  Recording changes
+    nothing: obs, reward, flags and state equal those of a twin without events bit for bit.  Switched off again, a further
+    step still works."""
+    from nascargymnasium_amd.batched import BatchedCarEnv
+    E, C = 8, 2
+    a, b = (BatchedCarEnv(E, C, os.path.join(TRACKS, "daytona.track"), device="cuda:0") for _ in range(2))
+    for env in (a, b):
+        env.set_fused_logic(fused)
+        env.set_rollout_streams(1)      # one shard: its range is the whole grid, so the rollout records the events too
+    a.reset()
+    b.set_state(a.get_state()); b.obs.copy_(a.obs)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    a.set_step_events(ev)
+
+    def mark():
+        m = torch.cuda.Event(enable_timing=True)
+        m.record()
+        return m
+
+    def same(marker):
+        torch.cuda.synchronize()
+        assert marker.elapsed_time(ev[0]) >= 0.0            # recorded by the engine, after the marker
+        for k in range(3):
+            assert ev[k].elapsed_time(ev[k + 1]) >= 0.0, k
+        assert ev[0].elapsed_time(ev[3]) > 0.0              # the step's kernels lie between the first and the last
+        assert torch.equal(a.obs, b.obs) and torch.equal(a.reward, b.reward)
+        assert torch.equal(a.car_flags, b.car_flags) and torch.equal(a.env_flags, b.env_flags)
+        assert torch.equal(a.get_state(), b.get_state())
+
+    a.obs.clone().add_(1)   # device work between set_step_events' own records and the marker: a stale ev[0] lies before it
+    m = mark()
+    for k in range(3):
+        for env in (a, b):
+            env.launch_step(env.policy_actions(3, seed=7, step=k).clone(), auto_reset=True)
+    same(m)
+    m = mark()
+    for env in (a, b):
+        env.rollout(3, 2, seed=7, step0=3)
+    same(m)
+    a.set_step_events(None)
+    for env in (a, b):
+        env.launch_step(env.policy_actions(3, seed=7, step=5).clone(), auto_reset=True)
+    torch.cuda.synchronize()
+    assert torch.equal(a.obs, b.obs) and torch.equal(a.get_state(), b.get_state())
+    a.close(); b.close()

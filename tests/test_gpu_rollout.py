@@ -130,3 +130,25 @@ def test_step_driven_equals_policy_plus_step(policy):
         assert torch.equal(a.car_flags, b.car_flags) and torch.equal(a.env_flags, b.env_flags), k
     assert torch.equal(a.get_state(), b.get_state())
     a.close(); b.close()
+
+
+@pytest.mark.parametrize("streams", [4, 1])
+def test_rollout_without_trajectory_keeps_the_last_step(streams):
+    """rollout(trajectory=False) writes every step over one record: what the engine holds afterwards equals record
+    K - 1 (and the final observation) of a twin's rollout(trajectory=True) from the same state, bit for bit."""
+    E, C, K = 16, 2, 20
+    a, b = _engine(["daytona.track"], E, C), _engine(["daytona.track"], E, C)
+    for e in (a, b):
+        e.set_rollout_streams(streams)
+    a.reset()
+    a.rollout(3, 30, seed=9, step0=0, auto_reset=True)      # leave the reset state
+    b.set_state(a.get_state()); b.obs.copy_(a.obs)
+    obs_a, rew_a, cf_a, ef_a = a.rollout(3, K, seed=9, step0=30, auto_reset=True, trajectory=False)
+    obs_b, Rb, CFb, EFb = b.rollout(3, K, seed=9, step0=30, auto_reset=True, trajectory=True)
+    torch.cuda.synchronize()
+    assert Rb.shape == (K, E, C) and rew_a.shape == (E, C)
+    assert torch.equal(a.reward, Rb[K - 1]) and torch.equal(a.car_flags, CFb[K - 1]) and torch.equal(a.env_flags, EFb[K - 1])
+    assert torch.equal(rew_a, Rb[K - 1]) and torch.equal(cf_a, CFb[K - 1]) and torch.equal(ef_a, EFb[K - 1])
+    assert torch.equal(a.obs, obs_b) and torch.equal(obs_a, obs_b)
+    assert torch.equal(a.get_state(), b.get_state())
+    a.close(); b.close()
